@@ -2,6 +2,7 @@
 """Throughput of the MI355X LightGlue matcher: image-pairs/s at N=2048 keypoints, d=256.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--npts N] [--workload W]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py spawns the N ranks itself
@@ -35,9 +36,21 @@ Training steps (reference gluefactory/train.py:430-470) through 
   object is the whole step's algorithmic flops against the f32 MFMA peak, and their CPU baseline
   the oracle's training step on one pair)
 
-Prints ONE JSON line on rank 0 with the metric, the attention kernel's roofline (in-library HIP
-events around every attention launch in the timed region; algorithmic flops per launch) and the
-CPU oracle's throughput on this host (rank 0, N=1 only, bounded sample).
+Prints ONE JSON line on rank 0 with the metric, ``ms_per_step`` (milliseconds per timed step) and
+the attention kernel's roofline (in-library HIP events around every attention launch in the timed
+region; algorithmic flops per launch).  A plain run does nothing else: set up, W warm-up steps,
+K timed steps, the result line.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes what the LAST timed step returned to its
+                    caller as DIR/<name>.npy (float32; integer arrays as float64, exact), at most
+                    64 MB in all: an array over its share of that budget is stored as a fixed,
+                    seeded sample of its flattened entries (``dump_sample_indices``).  Inputs and
+                    weights are seeded, so two builds run with the same arguments write comparable
+                    files.
+--full              also measures what takes runs of its own: the per-family kernel breakdown
+                    (GEMM / assignment, a few untimed steps with every kernel family evented) and
+                    the CPU oracle's throughput on this host (rank 0, N=1 only, bounded sample,
+                    --cpu-budget seconds).
 """
 import argparse
 import json
@@ -109,6 +122,47 @@ def gpu_pairs(B, N, dim, seed, device, size=(640.0, 640.0)):
         "keypoints0": k0, "keypoints1": k1, "descriptors0": d0, "descriptors1": d1,
         "view0": {"image_size": isz}, "view1": {"image_size": isz},
     }
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: under the 64 MB bound with room for the .npy headers
+DUMP_SEED = 20240229
+
+
+def dump_sample_indices(numel, count):
+    """The fixed sample of --dump-outputs: `count` sorted flat indices into an array of `numel`
+    entries (with repeats), from a CPU generator seeded by DUMP_SEED and the two sizes."""
+    g = torch.Generator().manual_seed(DUMP_SEED + numel % 1000003 + 7 * count)
+    return torch.sort(torch.randint(numel, (count,), generator=g)).values
+
+
+def dump_outputs(outdir, outputs):
+    """Write a step's outputs (name -> tensor, list of tensors, or number) as outdir/<name>.npy.
+    Floating arrays are stored as float32 (float64 stays), integer and bool arrays as float64.
+    Arrays are stored whole while they fit an equal share of DUMP_BUDGET_BYTES; a larger one is
+    stored as its entries at dump_sample_indices(numel, share)."""
+    os.makedirs(outdir, exist_ok=True)
+    flat = {}
+    for name, v in outputs.items():
+        if isinstance(v, (list, tuple)):
+            if not v or not all(isinstance(t, torch.Tensor) for t in v):
+                continue
+            v = torch.cat([t.detach().reshape(-1) for t in v])
+        elif not isinstance(v, torch.Tensor):
+            if not isinstance(v, (int, float)):
+                continue
+            v = torch.tensor(float(v), dtype=torch.float64)
+        v = v.detach()
+        if not (v.is_floating_point() and v.dtype == torch.float64):
+            v = v.to(torch.float32 if v.is_floating_point() else torch.float64)
+        flat[name] = v
+    if not flat:
+        return
+    share = DUMP_BUDGET_BYTES // len(flat)
+    for name, v in flat.items():
+        cap = share // v.element_size()
+        if v.numel() > cap:
+            v = v.reshape(-1)[dump_sample_indices(v.numel(), cap).to(v.device)]
+        np.save(os.path.join(outdir, name + ".npy"), v.cpu().numpy())
 
 
 def attention_flops_per_pair(N, d=256, L=9):
@@ -320,13 +374,21 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="pairs per GPU per step (default: the workload's)")
     ap.add_argument("--npts", type=int, default=None, help="keypoints per image (default: the workload's)")
     ap.add_argument("--chunk", type=int, default=32, help="configs3: largest chunk of pairs per forward")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of timed CPU-baseline work (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: the per-family kernel "
+                         "breakdown and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0,
+                    help="--full: seconds of timed CPU-baseline work (0 = skip)")
     ap.add_argument("--precision", default="auto", choices=["auto", "bf16x6"])
     ap.add_argument("--checkpointed", action="store_true",
                     help="--workload train: LightGlue conf checkpointed (layer recompute in the backward)")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="CPU/gloo rehearsal of the launch and gather logic with a stand-in matcher")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     b, n, _ = WORKLOADS[a.workload]
     a.batch = b if a.batch is None else a.batch
     a.npts = n if a.npts is None else a.npts
@@ -451,15 +513,19 @@ def run(args):
     result_kernels, roofline = None, None
     if not selftest:
         att_ms, att_n, att_fl, att_by = model.profile_read("attention")
-        # per-family breakdown from a separate, untimed pass with every family evented
-        bsteps = min(args.steps, 3)
-        model.profile_enable(True)
-        for _ in range(bsteps):
-            step()
-        sync()
-        gem_ms, gem_n, gem_fl, _ = model.profile_read("gemm")
-        asg_ms, asg_n, _, asg_by = model.profile_read("assign")
         model.profile_enable(False)
+        if args.dump_outputs and rank == 0:  # before anything else runs: the last timed step's outputs
+            dump_outputs(args.dump_outputs, pred)
+        if args.full:
+            # per-family breakdown from a separate, untimed pass with every family evented
+            bsteps = min(args.steps, 3)
+            model.profile_enable(True)
+            for _ in range(bsteps):
+                step()
+            sync()
+            gem_ms, gem_n, gem_fl, _ = model.profile_read("gemm")
+            asg_ms, asg_n, _, asg_by = model.profile_read("assign")
+            model.profile_enable(False)
         prec = model.last_precision_used
         peak, kname, peak_note = PEAKS[prec]
         if prec == "fp16x3" and os.environ.get("LG_ATTN_KERNEL") == "h3m":
@@ -487,14 +553,17 @@ def run(args):
         if wl == "configs3":
             roofline["flops_note"] = ("pruned forwards: each launch's flops over the kept points of the running pairs "
                                       "(per-pair counts copied at launch time, lg_profile_read)")
-        result_kernels = {
-            "attention_ms_per_step": round(att_ms / args.steps, 3),
-            "breakdown_note": f"gemm/assign from {bsteps} untimed steps with every kernel family evented",
-            "gemm_ms_per_step": round(gem_ms / bsteps, 3),
-            "gemm_tflops": round(gem_fl / (gem_ms * 1e-3) / 1e12, 2) if gem_ms > 0 else None,
-            "assign_ms_per_step": round(asg_ms / bsteps, 3),
-            "assign_gbs": round(asg_by / (asg_ms * 1e-3) / 1e9, 1) if asg_ms > 0 else None,
-        }
+        result_kernels = {"attention_ms_per_step": round(att_ms / args.steps, 3)}
+        if args.full:
+            result_kernels.update({
+                "breakdown_note": f"gemm/assign from {bsteps} untimed steps with every kernel family evented",
+                "gemm_ms_per_step": round(gem_ms / bsteps, 3),
+                "gemm_tflops": round(gem_fl / (gem_ms * 1e-3) / 1e12, 2) if gem_ms > 0 else None,
+                "assign_ms_per_step": round(asg_ms / bsteps, 3),
+                "assign_gbs": round(asg_by / (asg_ms * 1e-3) / 1e9, 1) if asg_ms > 0 else None,
+            })
+    elif args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pred)
     if distributed:  # max over ranks of the timed region
         t = torch.tensor([el], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -549,7 +618,7 @@ def run(args):
                                               "the kernels' live-row flops are in roofline.achieved")
     if wl == "configs3" and not selftest:
         result["config"]["pruning"] = "width 0.95, depth 0.95 (weights: weights.prune_recipe_state_dict)"
-    if rank == 0 and world == 1 and args.cpu_budget > 0 and wl == "configs2":
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0 and wl == "configs2":
         result["cpu_baseline"] = cpu_baseline(N, args.cpu_budget)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -687,6 +756,11 @@ def run_train(args, world, rank, local, distributed):
         t = torch.tensor([el], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:  # the last timed step's loss and, on the GPU, the gradients it left
+        out = {"loss": loss}
+        if not args.selftest_cpu:
+            out["grads"] = [p.grad for p in params if p.grad is not None]
+        dump_outputs(args.dump_outputs, out)
     pairs = B * args.steps * world
     tf = train_flops_per_pair(N, sg) * pairs / el / 1e12
     result = {
@@ -726,7 +800,7 @@ def run_train(args, world, rank, local, distributed):
     }
     if args.selftest_cpu:
         result["data"] += " [CPU self-test: float32 oracle step stand-in]"
-    if rank == 0 and world == 1 and args.cpu_budget > 0 and not args.selftest_cpu:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0 and not args.selftest_cpu:
         result["cpu_baseline"] = cpu_baseline_train(N, args.cpu_budget, sg)
     if rank == 0:
         print(json.dumps(result), flush=True)

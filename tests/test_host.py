@@ -231,6 +231,34 @@ def test_bench_training_ground_truth_is_one_to_one():
     assert bench.train_flops_per_pair(2048) > 3 * 9 * 76 * 2048 * 256 * 256
 
 
+def test_bench_dump_outputs_formats_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output becomes one <name>.npy in float32 (integers as float64,
+    exact); an array over its share of the byte budget is stored as the fixed seeded sample of its
+    flattened entries, so two dumps of equal outputs are equal file for file."""
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 4000)  # 4 outputs -> 1000 float32 entries each
+    g = torch.Generator().manual_seed(5)
+    big = torch.randn(3, 41, 37, generator=g)
+    out = {"matches0": torch.arange(-1, 23).reshape(2, 12), "scores": torch.rand(2, 12, generator=g, dtype=torch.float64),
+           "log_assignment": big, "ragged": [big[0, :5, :7], big[1, :3, :2]], "note": "skipped"}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["log_assignment.npy", "matches0.npy", "ragged.npy", "scores.npy"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert a["matches0"].dtype == np.float64 and (a["matches0"] == out["matches0"].numpy()).all()
+    assert a["scores"].dtype == np.float64 and a["scores"].shape == (2, 12)
+    assert a["ragged"].dtype == np.float32 and a["ragged"].shape == (5 * 7 + 3 * 2,)
+    idx = bench.dump_sample_indices(big.numel(), 1000)
+    assert a["log_assignment"].dtype == np.float32 and a["log_assignment"].shape == (1000,)
+    assert (a["log_assignment"] == big.reshape(-1)[idx].numpy()).all()
+    assert (idx[1:] >= idx[:-1]).all() and 0 <= int(idx[0]) and int(idx[-1]) < big.numel()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 4 * 4000 + 4 * 128
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+
+
 def test_layer_slices_gradient_matches_indexing():
     """lightglue._LayerSlices (loss(): the per-layer head inputs) gives the same slices and the same
     [B, L, M, D] gradient as indexing rd[:, i], including layers whose slice gets no gradient."""

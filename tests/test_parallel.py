@@ -76,7 +76,14 @@ def test_sharded_matches_equal_unsharded(tmp_path, mode):
     world = 2
     mp.spawn(_worker, args=(world, _free_port(), mode, str(tmp_path)), nprocs=world, join=True)
     matcher, data = _setup(prune=mode.endswith("prune"))
-    ref = matcher(data)
+    # the unsharded run on one thread like the workers: torch's CPU products sum in an order that
+    # depends on the thread count, and the comparison below is exact
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        ref = matcher(data)
+    finally:
+        torch.set_num_threads(threads)
     for r in range(world):
         res = torch.load(tmp_path / f"res{r}.pt", weights_only=True)
         for k in ("matches0", "matches1", "matching_scores0", "matching_scores1"):
@@ -158,6 +165,22 @@ def test_bench_spawns_gpus_ranks_itself():
     assert res["config"]["global_batch"] == 6
     assert "match_static" in res["config"]["parallelism"]
     assert res["value"] == pytest.approx(res["pairs_timed"] / (res["ms_per_step"] * res["steps"] / 1000.0), rel=1e-2)
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path, full):
+    """A plain run times --steps steps, reports ms_per_step and writes --dump-outputs; the CPU
+    baseline appears only with --full (CPU rehearsal with the stand-in matcher)."""
+    out = tmp_path / "dump"
+    res = _bench_json(["bench.py", "--gpus", "1", "--selftest-cpu", "--steps", "4", "--warmup", "1", "--batch", "2",
+                       "--npts", "16", "--cpu-budget", "0.05", "--dump-outputs", str(out)] + (["--full"] if full else []))
+    assert res["steps"] == 4 and res["pairs_timed"] == 4 * 2
+    assert res["ms_per_step"] >= 0 and res["value"] > 0  # the stand-in's steps take microseconds
+    assert ("cpu_baseline" in res) == full
+    assert sorted(os.listdir(out)) == ["matches0.npy", "matches1.npy", "matching_scores0.npy", "matching_scores1.npy"]
+    m0 = np.load(out / "matches0.npy")
+    assert m0.dtype == np.float64 and m0.shape == (2, 16) and (m0 == -1).all()
+    assert np.load(out / "matching_scores0.npy").dtype == np.float32
 
 
 def test_bench_under_torchrun_launcher():
