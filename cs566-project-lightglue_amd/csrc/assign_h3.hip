@@ -20,30 +20,13 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "h3_pipeline.h"
 #include "kernels.h"
-
-#ifndef LG_LA_ROWS
-// la write as whole 256-column tile rows assembled in LDS, stored as 16-byte-aligned chunks (the
-// N+1-float rows of the log assignment start at every alignment; 0: per-wave 64-column runs of
-// dword stores, the round-4 form -- the default: the aligned form measured 0.685 vs 0.655 ms for
-// the assignment pass on the same box, WRITE_SIZE 603 vs 593 MB; profiles/r05/la/)
-#define LG_LA_ROWS 0
-#endif
 
 namespace lg {
 
 namespace {
 constexpr int kSimTile = 256;
-constexpr int kLaPitch = kSimTile + 4;  // la row buffer pitch (floats): room for the alignment shift
-__device__ __forceinline__ int sim_xcd_remap(int id, int n) {
-  const int xcd = id & 7, local = id >> 3;
-  const int base = n >> 3, extra = n & 7;
-  return xcd * base + (xcd < extra ? xcd : extra) + local;
-}
-template <int N>
-__device__ __forceinline__ void sim_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // reductions over the 16 lanes of a DPP row (lanes sharing lane >> 4)
 __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, dppf<0xB1>(v));
@@ -122,13 +105,9 @@ __device__ __forceinline__ void argmax_rows(float& best, int& bi) {
 template <int MODE>
 __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
   constexpr int BM = kSimTile, BN = kSimTile, BK = kKB, NSTAGE = 2, NW = 16, WGN = 4;
-  constexpr int APT = BM * BK * 2, WPT = BN * BK * 2;
-  constexpr int STAGE_BYTES = 2 * APT + 2 * WPT, PPW = STAGE_BYTES / 1024 / NW;
-  // la pass: the la rows are assembled in LDS 128 tile rows at a time ([128][kLaPitch] floats)
-  constexpr int SMEM = MODE == 1 && LG_LA_ROWS ? (NSTAGE * STAGE_BYTES > 128 * kLaPitch * 4 ? NSTAGE * STAGE_BYTES
-                                                                                          : 128 * kLaPitch * 4)
-                                               : NSTAGE * STAGE_BYTES;
-  __shared__ __attribute__((aligned(1024))) char smem[SMEM];
+  using S = H3Stage<BM, BN, NW>;
+  constexpr int APT = S::APT, WPT = S::WPT, STAGE_BYTES = S::STAGE_BYTES, PPW = S::PPW;
+  __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave / WGN) * 64, wn0 = (wave % WGN) * 64;
@@ -143,7 +122,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
     tile = local % T;
   } else {
     b = blockIdx.x / T;
-    tile = sim_xcd_remap(blockIdx.x % T, T);
+    tile = xcd_remap(blockIdx.x % T, T);
   }
   const int tm = tile / ntn, tn = tile - tm * ntn;
   const int arow = b * M + tm * BM, wrow = g.B * M + b * N + tn * BN;  // plane-image rows
@@ -165,38 +144,33 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto frag = [&](const char* st, int t0, int r, int c) {
-    return *reinterpret_cast<const f16x8*>(st + t0 + r * (BK * 2) + ((c ^ plane_swz(r)) << 4));
-  };
   const int nk = 256 / BK;
   issue(0, 0);
   for (int kt = 0; kt < nk; ++kt) {
-    sim_wait_vm<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    ring_wait<NSTAGE, PPW>(0);
+    lds_barrier();
     if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
+    // h3_pipeline.h h3_mma_stage, kept in place: called as a function this kernel (at the 128-VGPR
+    // cap) spills 84 / 96 bytes per lane (stats / la pass) against 44 / 40 here
     const char* st = smem + (kt & 1) * STAGE_BYTES;
     const int c = lane >> 4, r16 = lane & 15;
     f16x8 ah[4], al[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      ah[i] = frag(st, 0, wm0 + i * 16 + r16, c);
-      al[i] = frag(st, APT, wm0 + i * 16 + r16, c);
+      ah[i] = h3_frag(st, 0, wm0 + i * 16 + r16, c);
+      al[i] = h3_frag(st, APT, wm0 + i * 16 + r16, c);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int r = wn0 + j * 16 + r16;
-      const f16x8 wh = frag(st, 2 * APT, r, c);
-      const f16x8 wl = frag(st, 2 * APT + WPT, r, c);
+      const f16x8 wh = h3_frag(st, 2 * APT, r, c);
+      const f16x8 wl = h3_frag(st, 2 * APT + WPT, r, c);
       const f16x8 whs = wh * (_Float16)kLoScale;  // exact: |md_h| <= 16
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i][j] = mfma_h3_16(ah[i], al[i], whs, wl, wh, acc[i][j]);
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  lds_barrier();
 
   // lane element (ti, tj, r): pair-local row i0 + 16 ti + 4 (lane >> 4) + r, column j0 + 16 tj + (lane & 15)
   const int i0 = tm * BM + wm0 + 4 * (lane >> 4), j0 = tn * BN + wn0 + (lane & 15);
@@ -285,56 +259,6 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
           acc[ti][tj][r] = (row_of(ti, r) < M && col_of(tj) < N) ? v : -INFINITY;
         }
       }
-#if LG_LA_ROWS
-    // la write: 128 tile rows per pass in LDS, each row's columns shifted by the row's own
-    // misalignment a (la rows are N+1 floats long), so that position p of the LDS row sits at the
-    // 16-byte-aligned address (row start - a) + p: every lane stores one aligned 16-byte chunk of
-    // a row (a 1 KiB run per wave instruction); the partial chunks at the two ends go out as
-    // dword stores
-    if (g.la) {
-      float* buf = reinterpret_cast<float*>(smem);
-      const int ncol = min(BN, N - tn * BN);  // valid columns of this tile (a multiple of 16)
-#pragma unroll 1
-      for (int p = 0; p < 2; ++p) {
-        __syncthreads();  // the previous pass's reads (and the k-loop's last LDS reads) are done
-        if ((wave / WGN) / 2 == p) {
-          const int rb = wm0 - 128 * p;
-#pragma unroll
-          for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int lr = rb + 16 * ti + 4 * (lane >> 4) + r;
-              const long long i = tm * BM + 128 * p + lr;
-              const int sh = (int)((((long long)b * (M + 1) + i) * (N + 1) + tn * BN) & 3);
-#pragma unroll
-              for (int tj = 0; tj < 4; ++tj) buf[lr * kLaPitch + wn0 + 16 * tj + (lane & 15) + sh] = acc[ti][tj][r];
-            }
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int q = 0; q < 8; ++q) {
-          const int lr = wave * 8 + q;
-          const int i = tm * BM + 128 * p + lr;
-          if (i >= M) break;  // wave-uniform; rows only grow with q
-          const long long o = ((long long)b * (M + 1) + i) * (N + 1) + tn * BN;
-          const int a = (int)(o & 3), last = a + ncol;
-          float* gb = g.la + (o - a);  // 16-byte aligned
-          const float* lb = buf + lr * kLaPitch;
-          auto chunk = [&](int c) {
-            const int p0 = 4 * c, lo = max(p0, a), hi = min(p0 + 4, last);
-            if (lo >= hi) return;
-            if (lo == p0 && hi == p0 + 4) {
-              st_stream(reinterpret_cast<f32x4*>(gb + p0), *reinterpret_cast<const f32x4*>(lb + p0));
-            } else {
-              for (int pp = lo; pp < hi; ++pp) st_stream(gb + pp, lb[pp]);
-            }
-          };
-          chunk(lane);
-          if (lane == 0) chunk(64);  // the tail chunk of a full misaligned row
-        }
-      }
-    }
-#else
     // la write: 32-row passes through a per-wave LDS transpose, one 256-byte row run per store
     if (g.la) {
       float* ep = reinterpret_cast<float*>(smem) + wave * (32 * 64);
@@ -360,7 +284,6 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
     }
-#endif
     __syncthreads();  // the transpose buffers become the argmax tables
     float* redf = reinterpret_cast<float*>(smem);
     // row argmax over the wave's columns (first index on ties) -> table [256 rows][4]

@@ -349,7 +349,7 @@ __device__ __forceinline__ float log_sigmoid(float x) {
 // arguments), y Phi(y) = y - y Phi(-y) for y >= 0.  Measured over every fp32 y in [-14, 14]:
 // |error| <= 2.4e-7 against fp64 (0.5 y (1 + erff(y / sqrt2)) itself: 4.5e-7).  ~15 VALU ops,
 // a third of erff's divergent two-branch polynomial -- the LN epilogue's GELU pass was 40 us of
-// the ffn.0 GEMM's 269 (tools/kbench_gemm.hip, LG_LN_PROBE).
+// the ffn.0 GEMM's 269 (tools/kbench_gemm.hip KB_LN with the since-removed LN probe builds).
 __device__ __forceinline__ float gelu_erf(float y) {
   const float z = fabsf(y) * 0.70710678118654752f;
   const float t = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.f));

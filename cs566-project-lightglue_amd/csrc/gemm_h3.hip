@@ -32,19 +32,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "h3_pipeline.h"
 #include "kernels.h"
 
 namespace lg {
 
 namespace {
 constexpr int TB = 256;  // column tile; rows_pad granule
-
-__device__ __forceinline__ int xcd_remap_h3(int id, int n, bool rev = false) {
-  const int xcd = id & 7, local = id >> 3;
-  const int base = n >> 3, extra = n & 7;
-  const int cnt = base + (xcd < extra ? 1 : 0);
-  return xcd * base + (xcd < extra ? xcd : extra) + (rev ? cnt - 1 - local : local);
-}
 
 __device__ __forceinline__ void head_row_base_h3(const HeadLayout& hl, int row, int& base, int& stride) {
   if (row < hl.B * hl.M) {
@@ -60,16 +54,6 @@ __device__ __forceinline__ void head_row_base_h3(const HeadLayout& hl, int row, 
 }
 }  // namespace
 
-#ifndef LG_LN_PROBE
-#define LG_LN_PROBE 0  // timing probes of the LN epilogue (tools/kbench_gemm.hip only): 1 no GELU, 2 no stores
-#endif
-#ifndef LG_GEMM_DIAG
-// timing probes of the k-loop (tools/kbench_gemm.hip only; results are wrong under 1, 2, 4):
-// 1 every tile reads one of 8 row panels (L2-resident A), 2 no k-tile copies, 4 no vmcnt waits,
-// 8 the copies issued by the first NW/4 waves only, 16 A pieces only, 32 W pieces only,
-// 64 only the first NSTAGE k-tiles copied (later ones re-read them: realistic operands, no copy stream)
-#define LG_GEMM_DIAG 0
-#endif
 #ifndef LG_GEMM_A_NT
 // non-temporal A-operand copies (and residual reads) for operands of at least LG_NT_MIN_MB
 // (gemm_h3): streamed once, they should not displace the weights and the attention's q/k/v in the
@@ -83,20 +67,15 @@ __device__ __forceinline__ void head_row_base_h3(const HeadLayout& hl, int row, 
 // later, after ~1.5 GB of other traffic; configs[2] +0.4 % same box (1263 -> 1268 pairs/s)
 #define LG_GEMM_RES_NT 1
 #endif
-#ifndef LG_GEMM_SETPRIO
-#define LG_GEMM_SETPRIO 0
-#endif
 #ifndef LG_GEMM_MF16
+// (The 0 path is built by nothing; taking it out moves the register allocation of the 256-row and
+// LayerNorm kernels -- the generic visit lambda no longer captures half / l32 -- and that build
+// measured 0.1-0.9 % slower on two boxes, so it stays until that is understood.)
 // MFMA shape: 1 = v_mfma_f32_16x16x32_f16 (one instruction per 32-k tile; on random operands the
 // chip sustains ~1.2x the flop rate of the 32x32x16 shape, tools/probe_mfma_shape.hip),
 // 0 = v_mfma_f32_32x32x16_f16
 #define LG_GEMM_MF16 1
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // BN x BM tile of (BM/64) x (BN/WN) waves, each 64 x WN (2 x WN/32 MFMA tiles of 32 x 32).
 // KS > 1 (single-wave tiles only): KS waves split the k-tiles of one tile, each with its own LDS
@@ -110,12 +89,8 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
   static_assert(KS == 1 || NW == 1, "split-k: single-wave tiles");
   constexpr int NJ = WN / 32;                // 32-column MFMA tiles per wave
   constexpr int BK = kKB;                    // k-tile = one k-block of the plane images (32)
-  constexpr int APT = BM * BK * 2;           // one A plane tile (bytes)
-  constexpr int WPT = BN * BK * 2;           // one W plane tile
-  constexpr int STAGE_BYTES = 2 * APT + 2 * WPT;
-  constexpr int PIECES = STAGE_BYTES / 1024; // 1 KiB LDS-DMA pieces per stage
-  constexpr int PPW = PIECES / NW;
-  static_assert(PIECES % NW == 0, "pieces per wave");
+  using S = H3Stage<BM, BN, NW>;
+  constexpr int APT = S::APT, WPT = S::WPT, STAGE_BYTES = S::STAGE_BYTES, PPW = S::PPW;
   constexpr int RING = NSTAGE * STAGE_BYTES;  // one k-split group's stages
   static_assert(KS == 1 || RING >= 64 * 64 * 4, "split-k: a partial accumulator fits the ring");
   __shared__ __attribute__((aligned(1024))) char smem[KS * RING];
@@ -140,7 +115,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
   const int eo_v = (EPI == EPI_QKV_ROT || EPI == EPI_CROSS_QKV) ? range_exponent(g.ro_v) : 0;
 
   const int num_m = (g.R + BM - 1) / BM, num_n = g.Nout / BN;
-  const int tile = xcd_remap_h3(blockIdx.x, num_m * num_n, g.reverse != 0);
+  const int tile = xcd_remap(blockIdx.x, num_m * num_n, g.reverse != 0);
   const int tm = tile / num_n, tn = tile - tm * num_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int nk = g.K / BK, nk0 = g.K0 / BK;
@@ -162,41 +137,16 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
   // 1 KiB pieces [A h | A l | W h | W l]; wave w copies pieces PPW*w .. PPW*w + PPW-1.
   const uint32_t voff = lane * 16;
   auto issue = [&](int kt, int stage) {
-#if LG_GEMM_DIAG & 2
-    return;
-#endif
-#if LG_GEMM_DIAG & 64
-    if (kt >= NSTAGE) return;  // real data in every stage, later k-tiles re-read it (same MFMA power)
-#endif
-#if LG_GEMM_DIAG & 8
-    constexpr int IW = NW / 4 > 0 ? NW / 4 : 1;  // issuing waves
-    if (wave >= IW) return;
-#pragma unroll
-    for (int i = 0; i < PIECES / IW; ++i) {
-      const int q = wave * (PIECES / IW) + i;
-#else
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
       const int q = wave * PPW + i;  // wave-uniform
-#endif
       const char* src;
-#if LG_GEMM_DIAG & 16
-      if (q >= 2 * (APT / 1024)) continue;  // A pieces only
-#endif
-#if LG_GEMM_DIAG & 32
-      if (q < 2 * (APT / 1024)) continue;   // W pieces only
-#endif
       if (q < 2 * (APT / 1024)) {
         const int pl = q / (APT / 1024), pc = q % (APT / 1024);
         const bool first = kt < nk0;
         const PlaneRef& A = first ? g.A0 : g.A1;
         const int kb = first ? kt : kt - nk0;
-#if LG_GEMM_DIAG & 1
-        const int am0 = m0 & 2047;
-#else
-        const int am0 = m0;
-#endif
-        src = reinterpret_cast<const char*>(A.p + pl * A.ps + ((size_t)kb * A.rows_pad + am0) * BK) + pc * 1024;
+        src = reinterpret_cast<const char*>(A.p + pl * A.ps + ((size_t)kb * A.rows_pad + m0) * BK) + pc * 1024;
       } else {
         const int qw = q - 2 * (APT / 1024);
         const int pl = qw / (WPT / 1024), pc = qw % (WPT / 1024);
@@ -241,27 +191,24 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
     }
   };
 
-  // fragment (row r, 16-byte k-chunk c) of the plane tile at byte offset t0 of a stage
-  auto frag = [&](const char* st, int t0, int r, int c) {
-    return *reinterpret_cast<const f16x8*>(st + t0 + r * (BK * 2) + ((c ^ plane_swz(r)) << 4));
-  };
   auto compute = [&](int stage) {
     const char* st = smem + ks * RING + stage * STAGE_BYTES;
     if constexpr (kMF16) {
-      // lane: row (lane & 15) of each 16-row block, k chunk lane >> 4 (k = 8c .. 8c+7)
+      // h3_pipeline.h h3_mma_stage, kept in place: called as a function, the eight split-k kernels no
+      // longer compile to the same code.  Lane: row (lane & 15) of each 16-row block, k chunk lane >> 4
       const int c = lane >> 4, r16 = lane & 15;
       f16x8 ah[TI], al[TI];
 #pragma unroll
       for (int i = 0; i < TI; ++i) {
         const int r = wm0 + i * 16 + r16;
-        ah[i] = frag(st, 0, r, c);
-        al[i] = frag(st, APT, r, c);
+        ah[i] = h3_frag(st, 0, r, c);
+        al[i] = h3_frag(st, APT, r, c);
       }
 #pragma unroll
       for (int j = 0; j < TJ; ++j) {
         const int r = wn0 + j * 16 + r16;
-        const f16x8 wh = frag(st, 2 * APT, r, c);
-        const f16x8 wl = frag(st, 2 * APT + WPT, r, c);
+        const f16x8 wh = h3_frag(st, 2 * APT, r, c);
+        const f16x8 wl = h3_frag(st, 2 * APT + WPT, r, c);
         const f16x8 whs = wh * (_Float16)kLoScale;  // exact: |W_h| < 16
 #pragma unroll
         for (int i = 0; i < TI; ++i) acc[i][j] = mfma_h3_16(ah[i], al[i], whs, wl, wh, acc[i][j]);
@@ -275,14 +222,14 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int r = wm0 + i * 32 + l32;
-        ah[i] = frag(st, 0, r, c);
-        al[i] = frag(st, APT, r, c);
+        ah[i] = h3_frag(st, 0, r, c);
+        al[i] = h3_frag(st, APT, r, c);
       }
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int r = wn0 + j * 32 + l32;
-        wh[j] = frag(st, 2 * APT, r, c);
-        wl[j] = frag(st, 2 * APT + WPT, r, c);
+        wh[j] = h3_frag(st, 2 * APT, r, c);
+        wl[j] = h3_frag(st, 2 * APT + WPT, r, c);
         whs[j] = wh[j] * (_Float16)kLoScale;  // exact: |W_h| < 16
       }
 #pragma unroll
@@ -311,30 +258,14 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
     if (kb + p < ke) issue(kb + p, p);
   for (int kt = kb; kt < ke; ++kt) {
     const int ahead = min(NSTAGE - 2, ke - 1 - kt);  // my k-tiles in flight beyond kt
-#if LG_GEMM_DIAG & 8
-    wait_vm<0>();
-#elif !(LG_GEMM_DIAG & 4)
-    if (NSTAGE >= 4 && ahead >= 2) wait_vm<2 * PPW>();
-    else if (NSTAGE >= 3 && ahead >= 1) wait_vm<PPW>();
-    else wait_vm<0>();
-#endif
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (KS == 1) __builtin_amdgcn_s_barrier();  // split-k groups are single waves
-    asm volatile("" ::: "memory");
+    ring_wait<NSTAGE, PPW>(ahead);
+    lds_barrier<KS == 1>();  // split-k groups are single waves
     if (kt + NSTAGE - 1 < ke) issue(kt + NSTAGE - 1, (kt - kb + NSTAGE - 1) % NSTAGE);
     if (kt == nk0 && e0 != e1) scale_acc(ldexpf(1.f, e0 - e1));  // A0 -> A1 units (exact; rare)
-#if LG_GEMM_SETPRIO
-    __builtin_amdgcn_s_setprio(1);  // keeps the MFMA cluster between the barriers (guide T5)
-#endif
     compute((kt - kb) % NSTAGE);
-#if LG_GEMM_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
   }
   if (KS > 1 && ke <= nk0 && e0 != e1) scale_acc(ldexpf(1.f, e0 - e1));  // a partial of A0 k-tiles only
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  lds_barrier();
   // waves running the epilogue: split-k tiles give each group 16 rows of the tile (4 groups, 16 x 16
   // MFMA tiles) or 32 (2 groups); otherwise a wave runs both 32-row passes of its own tile
   constexpr int EW = KS > 1 ? (kMF16 && KS >= 4 ? 4 : 2) : NW;
@@ -356,9 +287,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
 #pragma unroll
           for (int r = 0; r < TR; ++r, ++x) pp[x * 64 + lane] = acc[i][j][r];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
     if (ks >= EW) return;
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
@@ -464,7 +393,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       constexpr int jh = 0;  // WN == 64: one 64-column pass per row pass
-      if constexpr (kMF16 && !(LG_LN_PROBE & 1)) {
+      if constexpr (kMF16) {
         // rows 4 (lane >> 4) + r, r = 0..3, of each 16-row block, column 16 j + (lane & 15): the
         // normalisation and GELU run on row pairs (r, r + 1) with packed fp32 arithmetic
 #pragma unroll
@@ -486,11 +415,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
         visit(i, [&](int rr, int c, float v) {
           const int lr = wm0 + i * 32 + rr;
           const float y = (v - mean_s[lr]) * rstd_s[lr] * gj[c / LC] + bj[c / LC];
-#if LG_LN_PROBE & 1
-          ep[rr * 64 + (c ^ ((rr & 1) << 2))] = y;
-#else
           ep[rr * 64 + (c ^ ((rr & 1) << 2))] = gelu_erf(y);
-#endif
           return v;
         });
       }
@@ -504,7 +429,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
           const int sw = (rr & 1) << 2;
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(ep + rr * 64 + (cq ^ sw));
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(ep + rr * 64 + ((cq + 4) ^ sw));
-          if (!(LG_LN_PROBE & 2) && row < g.R && row_live(g.rm, row)) {
+          if (row < g.R && row_live(g.rm, row)) {
             f16x8 h, l;
             float vv[8];
 #pragma unroll

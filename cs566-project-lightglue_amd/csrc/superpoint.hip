@@ -21,20 +21,12 @@
 #include <cstring>
 
 #include "common.h"
+#include "h3_pipeline.h"
 #include "kernels.h"
 
 namespace lg {
 
 namespace {
-__device__ __forceinline__ int sp_xcd_remap(int id, int n) {
-  const int xcd = id & 7, local = id >> 3;
-  const int base = n >> 3, extra = n & 7;
-  return xcd * base + (xcd < extra ? xcd : extra) + local;
-}
-template <int N>
-__device__ __forceinline__ void sp_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // float -> unsigned with the same order (larger key <=> larger value)
 __device__ __forceinline__ unsigned order_key(float v) {
   const unsigned u = __float_as_uint(v);
@@ -129,11 +121,9 @@ template <int BN, int NSTAGE, bool POOL>
 __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Args g) {
   constexpr int BM = 256, BK = kKB;
   constexpr int WGN = BN / 64, NW = 4 * WGN;
-  constexpr int APT = BM * BK * 2, WPT = BN * BK * 2;
-  constexpr int STAGE_BYTES = 2 * APT + 2 * WPT;
-  constexpr int PIECES = STAGE_BYTES / 1024, PPW = PIECES / NW;
+  using S = H3Stage<BM, BN, NW>;
+  constexpr int APT = S::APT, WPT = S::WPT, STAGE_BYTES = S::STAGE_BYTES, PPW = S::PPW;
   constexpr int AP = 2 * APT / 1024;  // A pieces per stage (16 rows of one plane each)
-  static_assert(PIECES % NW == 0, "pieces per wave");
   static_assert(NW * 32 * 64 * 4 <= NSTAGE * STAGE_BYTES, "epilogue scratch");
   __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE_BYTES];
 
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
   const int H = g.H, W = g.W, Hp = H >> 1, Wp = W >> 1;
   const int R = POOL ? 4 * g.B * Hp * Wp : g.B * H * W;
   const int num_m = (R + BM - 1) / BM, num_n = g.Cout / BN;
-  const int tile = sp_xcd_remap(blockIdx.x, num_m * num_n);
+  const int tile = xcd_remap(blockIdx.x, num_m * num_n);
   const int tm = tile / num_n, tn = tile - tm * num_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int CB = g.Cin / BK, nk = 9 * CB;
@@ -214,27 +204,9 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto frag = [&](const char* st, int t0, int r, int c) {
-    return *reinterpret_cast<const f16x8*>(st + t0 + r * (BK * 2) + ((c ^ plane_swz(r)) << 4));
-  };
   auto compute = [&](int stage) {
     const char* st = smem + stage * STAGE_BYTES;
-    const int c = lane >> 4, r16 = lane & 15;
-    f16x8 ah[4], al[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      ah[i] = frag(st, 0, wm0 + i * 16 + r16, c);
-      al[i] = frag(st, APT, wm0 + i * 16 + r16, c);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = wn0 + j * 16 + r16;
-      const f16x8 wh = frag(st, 2 * APT, r, c);
-      const f16x8 wl = frag(st, 2 * APT + WPT, r, c);
-      const f16x8 whs = wh * (_Float16)kLoScale;  // exact: |W_h| < 16
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][j] = mfma_h3_16(ah[i], al[i], whs, wl, wh, acc[i][j]);
-    }
+    h3_mma_stage<S>(st, wm0, wn0, lane, acc);
   };
 
 #pragma unroll
@@ -242,17 +214,12 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
     if (p < nk) issue(p, p);
   for (int kt = 0; kt < nk; ++kt) {
     const int ahead = min(NSTAGE - 2, nk - 1 - kt);
-    if (NSTAGE >= 3 && ahead >= 1) sp_wait_vm<PPW>();
-    else sp_wait_vm<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    ring_wait<NSTAGE, PPW>(ahead);
+    lds_barrier();
     if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, (kt + NSTAGE - 1) % NSTAGE);
     compute(kt % NSTAGE);
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  lds_barrier();
 
   // epilogue: bias + ReLU (+ pool) -> planes, 16-byte stores through a per-wave LDS transpose
   float* ep = reinterpret_cast<float*>(smem) + wave * (32 * 64);
@@ -471,9 +438,8 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int r = wn0 + j * 16 + r16;
-      const int o = r * (BK * 2) + ((c ^ plane_swz(r)) << 4);
-      f.wh[j] = *reinterpret_cast<const f16x8*>(wb + o);
-      f.wl[j] = *reinterpret_cast<const f16x8*>(wb + WPT + o);
+      f.wh[j] = h3_frag(wb, 0, r, c);
+      f.wl[j] = h3_frag(wb, WPT, r, c);
     }
   };
   f32x4 acc[WMT][4];
@@ -484,11 +450,6 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
 #pragma unroll
       for (int i = 0; i < WMT; ++i) acc[i][j] = mfma_h3_16(f.ah[i], f.al[i], whs, f.wl[j], f.wh[j], acc[i][j]);
     }
-  };
-  auto barrier = [&] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
   };
 
   const int cq = (lane & 7) * 8;
@@ -532,10 +493,10 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
       for (int tap = 0; tap < 9; ++tap, ++gs) {
         // W(gs) complete (and with it the halo of this block, issued before it); issued after
         // it: W(gs + 1) and, at taps 1-2, the next halo (issued at tap 0)
-        if ((tap == 1 || tap == 2) && hnext) sp_wait_vm<PW + PH>();
-        else if (gs + 1 < S) sp_wait_vm<PW>();
-        else sp_wait_vm<0>();
-        barrier();
+        if ((tap == 1 || tap == 2) && hnext) dma_wait<PW + PH>();
+        else if (gs + 1 < S) dma_wait<PW>();
+        else dma_wait<0>();
+        lds_barrier();
         if (gs + 2 < S) issue_w_step(cur, nxt, cb * 9 + tap + 2, gs + 2);
         if (tap == 0 && hnext) {
           if (cb + 1 < CB) issue_halo(cur, cb + 1, (gcb + 1) & 1);
@@ -549,7 +510,7 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
     }
     // epilogue: bias + ReLU (+ pool) -> planes through a per-wave transpose in the halo buffer
     // just consumed (every wave past its last read of it: the barrier)
-    barrier();
+    lds_barrier();
     float* ep = reinterpret_cast<float*>(smem + ((k * CB + CB - 1) & 1) * HALO_BYTES) + wave * (EPR * 64);
     const int col0 = cur.n0 + wn0 + cq;
     if constexpr (!POOL) {

@@ -240,16 +240,17 @@ int main() {
     if (getenv("KB_CHAIN")) {
       // VERDICT r4 item 1(b), costing a chained ffn.3 -> next QKV kernel on 128-row panels (A of the
       // QKV phase resident in LDS): the 128 x 256 tile (8 waves) against the production 256 x 256
-      // tile.  Build with -DLG_GEMM_DIAG=32 to drop the A copies (the QKV phase's A from LDS).
+      // tile.  (The W-copies-only variant was an LG_GEMM_DIAG=32 build; that probe is gone, DESIGN.md §5
+      // "Round 5: the two GEMM levers" keeps its result.)
       if (s.K < 256) continue;
       ms = run_h3<256, 2, EPI_PROBE>(s, bias, Y, it, false, Yp); rep("256x256 k-loop only", ms, false);
-      ms = run_h3<256, 2>(s, bias, Y, it, false, Yp); rep("256x256 + fp32 out", ms, !LG_GEMM_DIAG);
-      ms = run_h3<256, 2>(s, bias, Y, it, true, Yp); rep("256x256 + fp32 + planes", ms, !LG_GEMM_DIAG);
+      ms = run_h3<256, 2>(s, bias, Y, it, false, Yp); rep("256x256 + fp32 out", ms, true);
+      ms = run_h3<256, 2>(s, bias, Y, it, true, Yp); rep("256x256 + fp32 + planes", ms, true);
       ms = run_h3<128, 2, EPI_PROBE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w k-loop only", ms, false);
-      ms = run_h3<128, 2, EPI_STORE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w + fp32 out", ms, !LG_GEMM_DIAG);
-      ms = run_h3<128, 2, EPI_STORE, 256>(s, bias, Y, it, true, Yp); rep("128x256 8w + fp32 + planes", ms, !LG_GEMM_DIAG);
+      ms = run_h3<128, 2, EPI_STORE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w + fp32 out", ms, true);
+      ms = run_h3<128, 2, EPI_STORE, 256>(s, bias, Y, it, true, Yp); rep("128x256 8w + fp32 + planes", ms, true);
       ms = run_h3<128, 3, EPI_PROBE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w 3 stages k-loop only", ms, false);
-      ms = run_h3<128, 3, EPI_STORE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w 3 stages + fp32", ms, !LG_GEMM_DIAG);
+      ms = run_h3<128, 3, EPI_STORE, 256>(s, bias, Y, it, false, Yp); rep("128x256 8w 3 stages + fp32", ms, true);
       continue;
     }
     if (getenv("KB_LN64")) {  // LN GEMM at 64-row vs 128-row tiles (k-loop and full)
@@ -265,7 +266,7 @@ int main() {
       CK(hipFree(gam)); CK(hipFree(bet));
       continue;
     }
-    if (getenv("KB_LN")) {  // LN epilogue probes (build with -DLG_LN_PROBE=0/1/2/3)
+    if (getenv("KB_LN")) {  // LN epilogue against the bare k-loop (the LG_LN_PROBE builds are gone: DESIGN.md §5)
       if (s.N != 512) continue;
       ms = run_ln<64, EPI_PROBE>(s, bias, nullptr, nullptr, Yp, it); rep("h3  128x512 x2, no epilogue", ms, false);
       float *gam, *bet;
@@ -276,18 +277,18 @@ int main() {
       CK(hipFree(gam)); CK(hipFree(bet));
       continue;
     }
-    if (small) {  // latency decomposition (build with -DLG_GEMM_DIAG=0 / 2 no copies / 4 no waits)
-      ms = run_h3<64, 2, EPI_STORE, 64, 64, 4>(s, bias, Y, it, false, Yp); rep("64x64 ks4, fp32 out", ms, !LG_GEMM_DIAG);
-      ms = run_h3<64, 2, EPI_STORE, 64, 64, 4>(s, bias, Y, it, true, Yp); rep("64x64 ks4, fp32 + planes", ms, !LG_GEMM_DIAG);
+    if (small) {  // small-tile launch shapes (the LG_GEMM_DIAG no-copy / no-wait builds are gone: DESIGN.md §5)
+      ms = run_h3<64, 2, EPI_STORE, 64, 64, 4>(s, bias, Y, it, false, Yp); rep("64x64 ks4, fp32 out", ms, true);
+      ms = run_h3<64, 2, EPI_STORE, 64, 64, 4>(s, bias, Y, it, true, Yp); rep("64x64 ks4, fp32 + planes", ms, true);
       ms = run_h3<64, 2, EPI_PROBE, 64, 64, 4>(s, bias, Y, it, false, Yp); rep("64x64 ks4, no epilogue", ms, false);
-      ms = run_h3<64, 4, EPI_STORE, 64, 64, 2>(s, bias, Y, it, false, Yp); rep("64x64 ks2, fp32 out", ms, !LG_GEMM_DIAG);
-      ms = run_h3<64, 4, EPI_STORE, 64, 64, 1>(s, bias, Y, it, false, Yp); rep("64x64 ks1, fp32 out", ms, !LG_GEMM_DIAG);
+      ms = run_h3<64, 4, EPI_STORE, 64, 64, 2>(s, bias, Y, it, false, Yp); rep("64x64 ks2, fp32 out", ms, true);
+      ms = run_h3<64, 4, EPI_STORE, 64, 64, 1>(s, bias, Y, it, false, Yp); rep("64x64 ks1, fp32 out", ms, true);
       continue;
     }
-    if (getenv("KB_QUICK")) {  // k-loop probes (build with -DLG_GEMM_DIAG=0/1/2)
+    if (getenv("KB_QUICK")) {  // k-loop against the full kernel (the LG_GEMM_DIAG probe builds are gone: DESIGN.md §5)
       if (s.K < 256) continue;
       ms = run_h3<256, 2, EPI_PROBE>(s, bias, Y, it, false, Yp); rep("h3  256x256x32 x2, no epilogue", ms, false);
-      ms = run_h3<256, 2>(s, bias, Y, it, true, Yp); rep("h3  256x256 + planes", ms, !LG_GEMM_DIAG);
+      ms = run_h3<256, 2>(s, bias, Y, it, true, Yp); rep("h3  256x256 + planes", ms, true);
       continue;
     }
     if (!only_stagger) {
