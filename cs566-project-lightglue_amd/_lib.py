@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LIGHTGLUE_MI355X_LIB", os.path.join(_HERE, "liblightglue_mi355x.so"))
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 LG_OK, LG_E_INVALID, LG_E_HIP, LG_E_WEIGHTS, LG_E_WORKSPACE, LG_E_INTERNAL = 0, -1, -2, -3, -4, -5
 
@@ -132,6 +132,9 @@ class LGInputs(ctypes.Structure):
         ("scales1", _P),
         ("oris1", _P),
         ("flags", ctypes.c_int32),
+        # ABI 11: per-pair keypoint counts of a ragged batch, device int32 [B]; NULL = every slot full
+        ("num_keypoints0", _P),
+        ("num_keypoints1", _P),
     ]
 
 

@@ -126,7 +126,7 @@ __global__ void logsig_kernel(const float* z, float* ls, int n) {
 // One wave per row: la row write (optional) + row max / first argmax of the inner block.
 template <bool FROM_LA>
 __global__ __launch_bounds__(256) void row_pass_kernel(const float* src, Stats st, const float* z0, float* la, int B, int M,
-                                                       int N, const int* Mb, const int* Nb) {
+                                                       int N, const int* Mb, const int* Nb, int fixed) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= B * M) return;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void row_pass_kernel(const float* src, Stats s
   if (lane == 0) {
     st.max0[row] = best;
     st.arg0[row] = bi;
-    if (lr) lr[ne] = log_sigmoid(-z0[row]);
+    if (lr) lr[fixed ? N : ne] = log_sigmoid(-z0[row]);  // fixed (ragged) layout: the dustbin column stays at N
   }
 }
 
@@ -162,6 +162,26 @@ __global__ void la_last_row_kernel(const float* z1, float* la, int B, int M, int
   const int me = Mb ? Mb[b] : M, ne = Nb ? Nb[b] : N;
   if (j > ne) return;
   la[((size_t)b * (M + 1) + me) * (N + 1) + j] = j < ne ? log_sigmoid(-z1[b * N + j]) : 0.f;
+}
+
+// The frame of a ragged batch's fixed-shape la (AssignArgs.fixed): everything outside pair b's
+// real block [Mb][Nb] -- dustbin column at N (rows < Mb), dustbin row at M (columns < Nb),
+// [M][N] = 0, every other entry -inf.  One thread per element of [B][M+1][N+1].
+__global__ void la_ragged_frame_kernel(const float* z0, const float* z1, float* la, int B, int M, int N, const int* Mb,
+                                       const int* Nb) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t per = (size_t)(M + 1) * (N + 1);
+  if (t >= (size_t)B * per) return;
+  const int b = (int)(t / per);
+  const int rem = (int)(t - (size_t)b * per);
+  const int i = rem / (N + 1), j = rem - i * (N + 1);
+  const int me = Mb[b], ne = Nb[b];
+  if (i < me && j < ne) return;  // the real block: written by the assignment passes
+  float v = -INFINITY;
+  if (i == M && j == N) v = 0.f;
+  else if (j == N && i < me) v = log_sigmoid(-z0[b * M + i]);
+  else if (i == M && j < ne) v = log_sigmoid(-z1[b * N + j]);
+  la[t] = v;
 }
 
 template <bool FROM_LA>
@@ -482,9 +502,10 @@ size_t filter_workspace_floats(int B, int M, int N) { return assign_workspace_fl
 template <bool FROM_LA>
 static hipError_t argmax_and_filter(const float* src, const Stats& s, const float* z0, float* la, int B, int M, int N,
                                     float th, int64_t* m0, int64_t* m1, float* s0, float* s1, hipStream_t st,
-                                    const int* Mb = nullptr, const int* Nb = nullptr) {
+                                    const int* Mb = nullptr, const int* Nb = nullptr, int fixed = 0) {
   const int nch = (M + CCH - 1) / CCH;
-  hipLaunchKernelGGL((row_pass_kernel<FROM_LA>), dim3((B * M + 3) / 4), dim3(256), 0, st, src, s, z0, la, B, M, N, Mb, Nb);
+  hipLaunchKernelGGL((row_pass_kernel<FROM_LA>), dim3((B * M + 3) / 4), dim3(256), 0, st, src, s, z0, la, B, M, N, Mb, Nb,
+                     fixed);
   hipLaunchKernelGGL((col_arg_partial_kernel<FROM_LA>), dim3((N + 255) / 256, nch, B), dim3(256), 0, st, src, s, M, N, Mb,
                      Nb);
   hipLaunchKernelGGL(col_arg_combine_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s, nch, N, B * N, Nb);
@@ -517,9 +538,15 @@ hipError_t assign_and_filter(const AssignArgs& a, hipStream_t st) {
                      a.Nb, s.cmax, s.clog);
   hipLaunchKernelGGL(logsig_kernel, dim3((B * M + 255) / 256), dim3(256), 0, st, a.z0, s.ls0, B * M);
   hipLaunchKernelGGL(logsig_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, a.z1, s.ls1, B * N);
-  if (a.la)
+  if (a.fixed && !a.Mb) return hipErrorInvalidValue;
+  if (a.la && a.fixed) {
+    const size_t n = (size_t)B * (M + 1) * (N + 1);
+    hipLaunchKernelGGL(la_ragged_frame_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.z0, a.z1, a.la, B, M,
+                       N, a.Mb, a.Nb);
+  } else if (a.la) {
     hipLaunchKernelGGL(la_last_row_kernel, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, a.z1, a.la, B, M, N, a.Mb,
                        a.Nb);
+  }
   if (fused) {
     const int k4 = (N + 255) / 256;
     if (k4 <= 1) launch_la_fused<1>(a, s, nch, st);
@@ -531,13 +558,15 @@ hipError_t assign_and_filter(const AssignArgs& a, hipStream_t st) {
                        a.s0, a.s1, nullptr, nullptr);
     return hipGetLastError();
   }
-  return argmax_and_filter<false>(a.sim, s, a.z0, a.la, B, M, N, a.th, a.m0, a.m1, a.s0, a.s1, st, a.Mb, a.Nb);
+  return argmax_and_filter<false>(a.sim, s, a.z0, a.la, B, M, N, a.th, a.m0, a.m1, a.s0, a.s1, st, a.Mb, a.Nb, a.fixed);
 }
 
 // similarity recomputed in two fp16x3 GEMM passes (assign_h3.hip) instead of materialised
 hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const unsigned* rtab, int slot, hipStream_t st) {
   const int B = a.B, M = a.M, N = a.N;
-  if (B * M == 0 || B * N == 0 || a.Mb || !sim_h3_supported(M, N)) return hipErrorInvalidValue;
+  // per-pair counts: only the fixed-shape layout of a ragged batch (the pruning path is unfused)
+  if (B * M == 0 || B * N == 0 || (a.Mb && !a.fixed) || (!a.Mb && a.fixed) || !sim_h3_supported(M, N))
+    return hipErrorInvalidValue;
   const Stats s = carve(a.ws, B, M, N);
   const int ntm = (M + 255) / 256;
   float* extra = a.ws + ((assign_workspace_floats(B, M, N) + 63) & ~size_t(63));
@@ -549,6 +578,8 @@ hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const u
   g.B = B;
   g.M = M;
   g.N = N;
+  g.Mb = a.Mb;
+  g.Nb = a.Nb;
   g.rowp = reinterpret_cast<float2*>(extra);
   g.pmax = s.pv;
   g.psum = reinterpret_cast<float*>(s.pi);  // the argmax index partials are not live yet
@@ -558,12 +589,17 @@ hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const u
   g.rlog = s.rlog;
   if ((e = sim_row_stats(g, st)) != hipSuccess) return e;
   hipLaunchKernelGGL(col_stats_combine_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s.pv, g.psum, ntm, N, B * N,
-                     nullptr, s.cmax, s.clog);
+                     a.Nb, s.cmax, s.clog);
   hipLaunchKernelGGL(logsig_kernel, dim3((B * M + 255) / 256), dim3(256), 0, st, a.z0, s.ls0, B * M);
   hipLaunchKernelGGL(logsig_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, a.z1, s.ls1, B * N);
-  if (a.la)
+  if (a.la && a.fixed) {
+    const size_t n = (size_t)B * (M + 1) * (N + 1);
+    hipLaunchKernelGGL(la_ragged_frame_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.z0, a.z1, a.la, B, M,
+                       N, a.Mb, a.Nb);
+  } else if (a.la) {
     hipLaunchKernelGGL(la_last_row_kernel, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, a.z1, a.la, B, M, N, nullptr,
                        nullptr);
+  }
   g.ls0 = s.ls0;
   g.cmax = s.cmax;
   g.clog = s.clog;
@@ -575,9 +611,9 @@ hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const u
   g.pi = s.pi;
   if ((e = sim_h3_pass(g, 1, st)) != hipSuccess) return e;
   if ((e = sim_row_arg(g, a.z0, s.max0, s.arg0, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(col_arg_combine_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s, ntm, N, B * N, nullptr);
+  hipLaunchKernelGGL(col_arg_combine_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s, ntm, N, B * N, a.Nb);
   hipLaunchKernelGGL(filter_kernel, dim3((B * (M + N) + 255) / 256), dim3(256), 0, st, s, B, M, N, a.th, a.m0, a.m1, a.s0,
-                     a.s1, nullptr, nullptr);
+                     a.s1, a.Mb, a.Nb);
   return hipGetLastError();
 }
 

@@ -102,7 +102,10 @@ __device__ __forceinline__ void argmax_rows(float& best, int& bi) {
 
 // 256 x 256 similarity tile, 16 waves of 64 x 64 (16x16x32 f16 MFMAs, three
 // per product), two 64 KiB LDS-DMA stages; MODE 0 = stats pass, 1 = la pass.
-template <int MODE>
+// RAGGED: rows / columns are bounded by the pair's own counts g.Mb[b] / g.Nb[b] (M, N stay the
+// layout capacities).  A separate instantiation: the uniform kernels sit at the 128-VGPR cap and
+// must not pay for the bounds.
+template <int MODE, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
   constexpr int BM = kSimTile, BN = kSimTile, BK = kKB, NSTAGE = 2, NW = 16, WGN = 4;
   using S = H3Stage<BM, BN, NW>;
@@ -125,6 +128,40 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
     tile = xcd_remap(blockIdx.x % T, T);
   }
   const int tm = tile / ntn, tn = tile - tm * ntn;
+  // the pair's bounds: read here, beside the range exponent -- h3_pipeline.h's counted wait allows
+  // no load between a stage's issue and its wait
+  int Mb = M, Nb = N;
+  if constexpr (RAGGED) {
+    Mb = g.Mb[b];
+    Nb = g.Nb[b];
+    // a tile wholly outside the pair's counts: no DMA is issued.  The combine kernels still merge
+    // this tile's partials for the live rows / columns it shares with other tiles: neutral values
+    if (tm * BM >= Mb || tn * BN >= Nb) {
+      if (tid < 256) {
+        const int i = tm * BM + tid;
+        if (i < Mb) {
+          if constexpr (MODE == 0) {
+            g.rowp[((size_t)b * M + i) * ntn + tn] = make_float2(-INFINITY, 0.f);
+          } else {
+            g.rbest[((size_t)b * M + i) * ntn + tn] = -INFINITY;
+            g.rbi[((size_t)b * M + i) * ntn + tn] = tn * BN;
+          }
+        }
+      } else if (tid < 512) {
+        const int j = tn * BN + tid - 256;
+        if (j < Nb) {
+          if constexpr (MODE == 0) {
+            g.pmax[((size_t)b * ntm + tm) * N + j] = -INFINITY;
+            g.psum[((size_t)b * ntm + tm) * N + j] = 0.f;
+          } else {
+            g.pv[((size_t)b * ntm + tm) * N + j] = -INFINITY;
+            g.pi[((size_t)b * ntm + tm) * N + j] = tm * BM;
+          }
+        }
+      }
+      return;
+    }
+  }
   const int arow = b * M + tm * BM, wrow = g.B * M + b * N + tn * BN;  // plane-image rows
   const float scale = ldexpf(1.f / kLoScale, 2 * range_slot_exp(g.rtab, g.slot));
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_char*)smem);
@@ -185,7 +222,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
       for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          acc[ti][tj][r] = (row_of(ti, r) < M && col_of(tj) < N) ? acc[ti][tj][r] * scale : -INFINITY;
+          acc[ti][tj][r] = (row_of(ti, r) < Mb && col_of(tj) < Nb) ? acc[ti][tj][r] * scale : -INFINITY;
     // rows: the wave's 64 columns (lane-local over tj, then the 16 lanes of the row)
 #pragma unroll
     for (int ti = 0; ti < 4; ++ti)
@@ -223,12 +260,12 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
       const int i = tm * BM + tid;
       float m = red[tid * 4].x, s = red[tid * 4].y;
       for (int w = 1; w < 4; ++w) lse_merge(m, s, red[tid * 4 + w].x, red[tid * 4 + w].y);
-      if (i < M) g.rowp[((size_t)b * M + i) * ntn + tn] = make_float2(m, s);
+      if (i < Mb) g.rowp[((size_t)b * M + i) * ntn + tn] = make_float2(m, s);
     } else if (tid < 512) {
       const int cl = tid - 256, j = tn * BN + cl;
       float m = red[1024 + cl].x, s = red[1024 + cl].y;
       for (int w = 1; w < 4; ++w) lse_merge(m, s, red[1024 + w * 256 + cl].x, red[1024 + w * 256 + cl].y);
-      if (j < N) {
+      if (j < Nb) {
         g.pmax[((size_t)b * ntm + tm) * N + j] = m;
         g.psum[((size_t)b * ntm + tm) * N + j] = s;
       }
@@ -239,7 +276,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
     float cm[4], cl[4], l1[4];
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) {
-      const int j = min(col_of(tj), N - 1);
+      const int j = min(col_of(tj), Nb - 1);  // a live column (Nb >= 1 here): dead ones hold stale statistics
       cm[tj] = g.cmax[(size_t)b * N + j];
       cl[tj] = g.clog[(size_t)b * N + j];
       l1[tj] = g.ls1[(size_t)b * N + j];
@@ -248,7 +285,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
     for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int i = min(row_of(ti, r), M - 1);
+        const int i = min(row_of(ti, r), Mb - 1);
         const float rm = g.rmax[(size_t)b * M + i], rl = g.rlog[(size_t)b * M + i], l0 = g.ls0[(size_t)b * M + i];
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) {
@@ -256,7 +293,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
           const float s0 = (x - rm) - rl;
           const float s1 = (x - cm[tj]) - cl[tj];
           const float v = (s0 + s1) + (l0 + l1[tj]);
-          acc[ti][tj][r] = (row_of(ti, r) < M && col_of(tj) < N) ? v : -INFINITY;
+          acc[ti][tj][r] = (row_of(ti, r) < Mb && col_of(tj) < Nb) ? v : -INFINITY;
         }
       }
     // la write: 32-row passes through a per-wave LDS transpose, one 256-byte row run per store
@@ -279,7 +316,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
         for (int rr = 0; rr < 32; ++rr) {
           const int i = tm * BM + wm0 + 32 * p + rr;
           const float v = ep[rr * 64 + (lane ^ ((rr & 1) << 2))];
-          if (i < M && j < N) st_stream(g.la + ((size_t)b * (M + 1) + i) * (N + 1) + j, v);
+          if (i < Mb && j < Nb) st_stream(g.la + ((size_t)b * (M + 1) + i) * (N + 1) + j, v);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
@@ -324,7 +361,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
       float best = redf[tid * 4];
       int bi = redi[tid * 4];
       for (int w = 1; w < 4; ++w) argmax_merge(best, bi, redf[tid * 4 + w], redi[tid * 4 + w]);
-      if (i < M) {
+      if (i < Mb) {
         g.rbest[((size_t)b * M + i) * ntn + tn] = best;
         g.rbi[((size_t)b * M + i) * ntn + tn] = bi;
       }
@@ -333,7 +370,7 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
       float best = redf[1024 + lc];
       int bi = redi[1024 + lc];
       for (int w = 1; w < 4; ++w) argmax_merge(best, bi, redf[1024 + w * 256 + lc], redi[1024 + w * 256 + lc]);
-      if (j < N) {
+      if (j < Nb) {
         g.pv[((size_t)b * ntm + tm) * N + j] = best;
         g.pi[((size_t)b * ntm + tm) * N + j] = bi;
       }
@@ -342,9 +379,11 @@ __global__ __launch_bounds__(1024) void sim_h3_kernel(SimH3Args g) {
 }
 
 // rows: merge the ntn tile partials in column order
-__global__ void sim_row_stats_kernel(const float2* rowp, int BM, int ntn, float* rmax, float* rlog) {
+__global__ void sim_row_stats_kernel(const float2* rowp, int BM, int ntn, float* rmax, float* rlog, int M,
+                                     const int* Mb) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= BM) return;
+  if (Mb && t % M >= Mb[t / M]) return;  // a ragged batch: dead rows have no partials
   float m = rowp[(size_t)t * ntn].x, s = rowp[(size_t)t * ntn].y;
   for (int k = 1; k < ntn; ++k) lse_merge<false>(m, s, rowp[(size_t)t * ntn + k].x, rowp[(size_t)t * ntn + k].y);
   rmax[t] = m;
@@ -352,9 +391,10 @@ __global__ void sim_row_stats_kernel(const float2* rowp, int BM, int ntn, float*
 }
 // rows: first argmax over the tile partials in column order (strictly greater wins); la dustbin
 __global__ void sim_row_arg_kernel(const float* rbest, const int* rbi, int B, int M, int N, int ntn, const float* z0,
-                                   float* max0, int* arg0, float* la) {
+                                   float* max0, int* arg0, float* la, const int* Mb) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= B * M) return;
+  if (Mb && t % M >= Mb[t / M]) return;
   float best = rbest[(size_t)t * ntn];
   int bi = rbi[(size_t)t * ntn];
   for (int k = 1; k < ntn; ++k) {
@@ -379,22 +419,28 @@ hipError_t sim_h3_pass(const SimH3Args& a, int mode, hipStream_t st) {
   const int ntm = (a.M + kSimTile - 1) / kSimTile, ntn = (a.N + kSimTile - 1) / kSimTile;
   if (a.M % 16 || a.N % 16 || a.P.rows_pad < a.B * (a.M + a.N) + kSimTile) return hipErrorInvalidValue;
   const dim3 grid(ntm * ntn * a.B), block(1024);
-  if (mode == 0) hipLaunchKernelGGL(sim_h3_kernel<0>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(sim_h3_kernel<1>, grid, block, 0, st, a);
+  if ((a.Mb == nullptr) != (a.Nb == nullptr)) return hipErrorInvalidValue;
+  if (a.Mb) {
+    if (mode == 0) hipLaunchKernelGGL((sim_h3_kernel<0, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((sim_h3_kernel<1, true>), grid, block, 0, st, a);
+  } else {
+    if (mode == 0) hipLaunchKernelGGL((sim_h3_kernel<0, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((sim_h3_kernel<1, false>), grid, block, 0, st, a);
+  }
   return hipGetLastError();
 }
 
 hipError_t sim_row_stats(const SimH3Args& a, hipStream_t st) {
   const int ntn = (a.N + kSimTile - 1) / kSimTile, BM = a.B * a.M;
   hipLaunchKernelGGL(sim_row_stats_kernel, dim3((BM + 255) / 256), dim3(256), 0, st, a.rowp, BM, ntn,
-                     const_cast<float*>(a.rmax), const_cast<float*>(a.rlog));
+                     const_cast<float*>(a.rmax), const_cast<float*>(a.rlog), a.M, a.Mb);
   return hipGetLastError();
 }
 
 hipError_t sim_row_arg(const SimH3Args& a, const float* z0, float* max0, int* arg0, hipStream_t st) {
   const int ntn = (a.N + kSimTile - 1) / kSimTile, BM = a.B * a.M;
   hipLaunchKernelGGL(sim_row_arg_kernel, dim3((BM + 255) / 256), dim3(256), 0, st, a.rbest, a.rbi, a.B, a.M, a.N, ntn, z0,
-                     max0, arg0, a.la);
+                     max0, arg0, a.la, a.Mb);
   return hipGetLastError();
 }
 

@@ -15,11 +15,13 @@ namespace lg {
 // With the reference's default init the condition term reaches |2000|, so a single rounding
 // difference moves the phase by ~1e-4 rad; mirroring the order keeps the phases bit-exact.
 // ----------------------------------------------------------------------------------------
-__global__ void kpt_extent_kernel(const float* kpts, int n, float* size_out) {
+__global__ void kpt_extent_kernel(const float* kpts, int n, float* size_out, const int* cnt) {
   // size = 1 + max - min over the pair's keypoints (lightglue.py:25-26); one block per pair.
+  // cnt: the pair's real points (a ragged batch); the slot stride stays n
   const int b = blockIdx.x;
+  const int ne = cnt ? cnt[b] : n;
   float mx[2] = {-INFINITY, -INFINITY}, mn[2] = {INFINITY, INFINITY};
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+  for (int i = threadIdx.x; i < ne; i += blockDim.x) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const float v = kpts[((size_t)b * n + i) * 2 + c];
@@ -49,6 +51,11 @@ __global__ void pe_kernel(PEArgs a) {
   const int pt = gid >> 5;
   if (pt >= a.B * a.n) return;
   const int b = pt / a.n;
+  int nc = a.n;  // the condition: the pair's own keypoint count
+  if (a.cnt) {
+    nc = a.cnt[b];
+    if (pt - b * a.n >= nc) return;  // padding of a ragged batch
+  }
   const float w = a.size[b * 2 + 0], h = a.size[b * 2 + 1];
   const float scale = div_rn(fmaxf(w, h), 2.f);
   float x[4];
@@ -61,7 +68,7 @@ __global__ void pe_kernel(PEArgs a) {
   const float* wr = a.Wr + f * a.m_in;
   float p = mul_rn(x[0], wr[0]);
   for (int k = 1; k < a.m_in; ++k) p = __fmaf_rn(x[k], wr[k], p);
-  const float cond = add_rn(mul_rn((float)a.n, a.Wc[f]), a.bc[f]);  // relu(n) = n
+  const float cond = add_rn(mul_rn((float)nc, a.Wc[f]), a.bc[f]);  // relu(n) = n
   p = add_rn(p, cond);
   a.cosb[(size_t)pt * kFreq + f] = cosf(p);
   a.sinb[(size_t)pt * kFreq + f] = sinf(p);
@@ -83,6 +90,11 @@ __global__ void pe2_kernel(PEArgs a0, PEArgs a1) {
   const int pt = gid >> 5;
   if (pt >= a.B * a.n) return;
   const int b = pt / a.n;
+  int nc = a.n;  // the condition: the pair's own keypoint count
+  if (a.cnt) {
+    nc = a.cnt[b];
+    if (pt - b * a.n >= nc) return;  // padding of a ragged batch
+  }
   const float w = a.size[b * 2 + 0], h = a.size[b * 2 + 1];
   const float scale = div_rn(fmaxf(w, h), 2.f);
   float x[4];
@@ -95,7 +107,7 @@ __global__ void pe2_kernel(PEArgs a0, PEArgs a1) {
   const float* wr = a.Wr + f * a.m_in;
   float p = mul_rn(x[0], wr[0]);
   for (int k = 1; k < a.m_in; ++k) p = __fmaf_rn(x[k], wr[k], p);
-  const float cond = add_rn(mul_rn((float)a.n, a.Wc[f]), a.bc[f]);  // relu(n) = n
+  const float cond = add_rn(mul_rn((float)nc, a.Wc[f]), a.bc[f]);  // relu(n) = n
   p = add_rn(p, cond);
   a.cosb[(size_t)pt * kFreq + f] = cosf(p);
   a.sinb[(size_t)pt * kFreq + f] = sinf(p);
@@ -108,9 +120,9 @@ hipError_t positional_encoding2(const PEArgs& a0, const PEArgs& a1, hipStream_t 
   return hipGetLastError();
 }
 
-hipError_t kpt_extent(const float* kpts, int B, int n, float* size_out, hipStream_t st) {
+hipError_t kpt_extent(const float* kpts, int B, int n, float* size_out, hipStream_t st, const int* cnt) {
   if (B == 0) return hipSuccess;
-  hipLaunchKernelGGL(kpt_extent_kernel, dim3(B), dim3(256), 0, st, kpts, n, size_out);
+  hipLaunchKernelGGL(kpt_extent_kernel, dim3(B), dim3(256), 0, st, kpts, n, size_out, cnt);
   return hipGetLastError();
 }
 
@@ -217,7 +229,8 @@ hipError_t gemv_256_masked(const float* x, const float* w, const float* b, float
 }
 
 // the same over two row sources in one launch: rows [0, r0) of x0, then rows [0, r1) of x1 into
-// y[0 .. r0 + r1); each source's rows are tested against rm with their own index (as two calls)
+// y[0 .. r0 + r1); rm is tested with the row's index in y (the GEMM row order: x0 holds image 0's
+// rows, x1 image 1's -- the masks of a ragged batch address the rows that way)
 __global__ __launch_bounds__(256) void gemv256_2_kernel(const float* x0, int r0, const float* x1, int r1, const float* w,
                                                         const float* b, float* y, RowMask rm) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -225,7 +238,7 @@ __global__ __launch_bounds__(256) void gemv256_2_kernel(const float* x0, int r0,
   if (row >= r0 + r1) return;
   const bool second = row >= r0;
   const int sr = second ? row - r0 : row;
-  if (!row_live(rm, sr)) return;
+  if (!row_live(rm, row)) return;
   const float* x = (second ? x1 : x0) + (size_t)sr * kDim;
   const f32x4 xv = *reinterpret_cast<const f32x4*>(x + lane * 4);
   const f32x4 wv = *reinterpret_cast<const f32x4*>(w + lane * 4);
@@ -357,9 +370,90 @@ hipError_t prune_init(const SegLayout& L, int* cnt, int* act, int* stop, int n_l
   return hipGetLastError();
 }
 
+// a ragged batch: the counts come from the caller (clamped here; never read on the host)
+__global__ void prune_init_counts_kernel(SegLayout L, const int* n0, const int* n1, int* cnt, int* cnt0, int* act,
+                                         int* stop, int n_layers, int* ind) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int R = L.B * (L.M0 + L.N0);
+  if (ind && t < R) {
+    int local;
+    (void)seg_of_row(L, t, local);
+    ind[t] = local;
+  }
+  if (t < L.B) {
+    int a = min(max(n0[t], 0), L.M0), b = min(max(n1[t], 0), L.N0);
+    if (a == 0 || b == 0) a = b = 0;  // an empty image: the pair has no matches, nothing of it runs
+    cnt[t] = cnt0[t] = a;
+    cnt[L.B + t] = cnt0[L.B + t] = b;
+    act[t] = 1;
+    stop[t] = n_layers - 1;
+  }
+}
+
+hipError_t prune_init_counts(const SegLayout& L, const int* n0, const int* n1, int* cnt, int* cnt0, int* act, int* stop,
+                             int n_layers, int* ind, hipStream_t st) {
+  const int T = ind ? L.B * (L.M0 + L.N0) : L.B;
+  hipLaunchKernelGGL(prune_init_counts_kernel, dim3((T + 255) / 256), dim3(256), 0, st, L, n0, n1, cnt, cnt0, act, stop,
+                     n_layers, ind);
+  return hipGetLastError();
+}
+
+__global__ void ragged_pad_outputs_kernel(SegLayout L, const int* cnt0, int64_t* m0, int64_t* m1, float* s0, float* s1,
+                                          int64_t* prune0, int64_t* prune1) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= L.B * (L.M0 + L.N0)) return;
+  int local;
+  const int s = seg_of_row(L, r, local);
+  if (local < cnt0[s]) return;
+  if (s < L.B) {
+    m0[r] = -1;
+    s0[r] = 0.f;
+    if (prune0) prune0[r] = 0;
+  } else {
+    const int u = r - L.B * L.M0;
+    m1[u] = -1;
+    s1[u] = 0.f;
+    if (prune1) prune1[u] = 0;
+  }
+}
+
+hipError_t ragged_pad_outputs(const SegLayout& L, const int* cnt0, int64_t* m0, int64_t* m1, float* s0, float* s1,
+                              int64_t* prune0, int64_t* prune1, hipStream_t st) {
+  const int R = L.B * (L.M0 + L.N0);
+  if (R == 0) return hipSuccess;
+  hipLaunchKernelGGL(ragged_pad_outputs_kernel, dim3((R + 255) / 256), dim3(256), 0, st, L, cnt0, m0, m1, s0, s1, prune0,
+                     prune1);
+  return hipGetLastError();
+}
+
+// max |x| over the live rows only: padding of a ragged batch never reaches the range table
+__global__ __launch_bounds__(256) void range_absmax_rows_kernel(const float* x, int R, int K, int ld, int row0, RowMask rm,
+                                                                unsigned* tab, int slot) {
+  float m = 0.f;
+  const int q = K / 4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)R * q; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / q), c = (int)(i % q) * 4;
+    if (!row_live(rm, row0 + r)) continue;
+    const float* p = x + (size_t)r * ld + c;
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fmaxf(fabsf(p[2]), fabsf(p[3]))));
+  }
+  range_commit(RangeOut{tab, -1, -1, 0.f, 0.f, 0.f, slot, 1}, m, 0);
+}
+
+hipError_t range_absmax_rows(const float* x, int R, int K, int ld, int row0, const RowMask& rm, unsigned* tab, int slot,
+                             hipStream_t st) {
+  if (R <= 0) return hipSuccess;
+  if (K % 4) return hipErrorInvalidValue;
+  const size_t n = (size_t)R * (K / 4);
+  hipLaunchKernelGGL(range_absmax_rows_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, st, x,
+                     R, K, ld, row0, rm, tab, slot);
+  return hipGetLastError();
+}
+
 // one workgroup per pair
 __global__ __launch_bounds__(256) void stop_decide_kernel(const float* token, const int* cnt, int* act, int* stop,
-                                                          SegLayout L, float thr, float depth_conf, int layer) {
+                                                          SegLayout L, float thr, float depth_conf, int layer,
+                                                          const int* cnt0) {
   __shared__ int red[4];
   const int b = blockIdx.x;
   if (!act[b]) return;
@@ -375,7 +469,8 @@ __global__ __launch_bounds__(256) void stop_decide_kernel(const float* token, co
   if (threadIdx.x == 0) {
     const int c = red[0] + red[1] + red[2] + red[3];
     // 1.0 - (confidences < threshold).float().sum() / num_points, num_points = m + n (:602-605)
-    const float ratio = 1.0f - (float)c / (float)(L.M0 + L.N0);
+    const int num_points = cnt0 ? cnt0[b] + cnt0[L.B + b] : L.M0 + L.N0;  // a ragged pair: its own m + n
+    const float ratio = 1.0f - (float)c / (float)num_points;
     if (ratio > depth_conf) {
       act[b] = 0;
       stop[b] = layer;
@@ -384,8 +479,9 @@ __global__ __launch_bounds__(256) void stop_decide_kernel(const float* token, co
 }
 
 hipError_t stop_decide(const float* token, const int* cnt, int* act, int* stop, const SegLayout& L, float thr,
-                       float depth_conf, int layer, hipStream_t st) {
-  hipLaunchKernelGGL(stop_decide_kernel, dim3(L.B), dim3(256), 0, st, token, cnt, act, stop, L, thr, depth_conf, layer);
+                       float depth_conf, int layer, hipStream_t st, const int* cnt0) {
+  hipLaunchKernelGGL(stop_decide_kernel, dim3(L.B), dim3(256), 0, st, token, cnt, act, stop, L, thr, depth_conf, layer,
+                     cnt0);
   return hipGetLastError();
 }
 

@@ -220,12 +220,15 @@ struct PEArgs {
   float* cosb;         // [B*n][32]
   float* sinb;
   int B, n, m_in;
+  const int* cnt;      // [B] or null: per-pair counts of a ragged batch -- the condition is the pair's
+                       // own count (not the capacity n) and padded points are skipped
 };
 hipError_t positional_encoding(const PEArgs& a, hipStream_t st);
 // both images in one launch
 hipError_t positional_encoding2(const PEArgs& a0, const PEArgs& a1, hipStream_t st);
 // size = 1 + max - min of each pair's keypoints (normalize_keypoints fallback, lightglue.py:25-26)
-hipError_t kpt_extent(const float* kpts, int B, int n, float* size_out, hipStream_t st);
+// cnt (nullable): per-pair counts, the reduction covers real points only
+hipError_t kpt_extent(const float* kpts, int B, int n, float* size_out, hipStream_t st, const int* cnt = nullptr);
 
 // In place (planes == null, PREC_X6) or into a plane image of K = 512 (PREC_H3).
 bool gemm_h3_ln_split(int R);
@@ -249,14 +252,19 @@ struct AssignArgs {
   int64_t* m0; int64_t* m1; float* s0; float* s1;
   const int* Mb;      // per-pair kept counts (batched pruning; null: M, N for every pair); la
   const int* Nb;      // then holds pair b's [Mb+1][Nb+1] block with the capacity strides
+  int fixed;          // with Mb / Nb (a ragged batch without pruning): la keeps the full [M+1][N+1]
+                      // shape -- real block at i < Mb, j < Nb, dustbin column at N (i < Mb), dustbin
+                      // row at M (j < Nb), [M][N] = 0, everything else -inf
 };
 size_t assign_workspace_floats(int B, int M, int N);
 hipError_t assign_and_filter(const AssignArgs& a, hipStream_t st);
 // The same with the similarity recomputed inside two fp16x3 GEMM passes instead of materialised
 // (assign_h3.hip): P = plane image of md (rows: image 0 rows of pair b at b*M, image 1 rows at
 // B*M + b*N; |md| <= 16 after its range exponent E[slot]), rows_pad >= B*(M+N) + 256, M and N
-// multiples of 16, no per-pair counts.  a.sim is not read; a.ws needs assign_workspace_floats +
-// sim_h3_workspace_floats.
+// multiples of 16.  a.sim is not read; a.ws needs assign_workspace_floats +
+// sim_h3_workspace_floats.  Per-pair counts (Mb / Nb, a ragged batch: AssignArgs.fixed) bound every
+// row / column test; M and N stay the layout capacities, and rows >= Mb[b] / columns >= Nb[b] of
+// the plane image (stale workspace) only ever reach accumulator elements that are masked.
 struct SimH3Args {
   PlaneRef P;
   const unsigned* rtab;
@@ -269,6 +277,7 @@ struct SimH3Args {
   float* la;                          // [B][M+1][N+1] or null
   float* rbest; int* rbi;             // la pass: [B][M][ntn] row argmax per column tile
   float* pv; int* pi;                 //          [B][ntm][N] column argmax per row tile
+  const int* Mb; const int* Nb;       // per-pair counts [B] (nullable: M, N for every pair)
 };
 bool sim_h3_supported(int M, int N);
 size_t sim_h3_workspace_floats(int B, int M, int N);
@@ -309,10 +318,23 @@ hipError_t gather_rows(float* dst, const float* src, const int* idx, int rows, i
 // ---- Point pruning and early stop for any batch size: layout and masks above (RowMask) -----
 // initial state: cnt = slot sizes, act = 1, stop = L-1, ind = 0, 1, 2, .. per segment
 hipError_t prune_init(const SegLayout& L, int* cnt, int* act, int* stop, int n_layers, int* ind, hipStream_t st);
+// the same for a ragged batch: cnt (and cnt0, the copy the early stop divides by) = the caller's
+// per-pair counts n0 / n1 [B] clamped to [0, capacity]; a pair with an empty image has both counts
+// zeroed (nothing of it is computed).  ind is nullable (no width pruning).
+hipError_t prune_init_counts(const SegLayout& L, const int* n0, const int* n1, int* cnt, int* cnt0, int* act, int* stop,
+                             int n_layers, int* ind, hipStream_t st);
+// padded points of a ragged batch (local index >= cnt0 of their segment): matches -1, scores 0,
+// prune 0 (prune0 / prune1 nullable)
+hipError_t ragged_pad_outputs(const SegLayout& L, const int* cnt0, int64_t* m0, int64_t* m1, float* s0, float* s1,
+                              int64_t* prune0, int64_t* prune1, hipStream_t st);
+// max |x| over the live rows of [R][K] (row stride ld; mask rows are row0 + r) -> M[slot]
+hipError_t range_absmax_rows(const float* x, int R, int K, int ld, int row0, const RowMask& rm, unsigned* tab, int slot,
+                             hipStream_t st);
 // early stop (check_if_stop :595-606, thresholds :581-584): per running pair, ratio =
-// 1 - #(token < thr over its kept points) / (M0 + N0); ratio > depth_conf stops it at `layer`
+// 1 - #(token < thr over its kept points) / (M0 + N0); ratio > depth_conf stops it at `layer`.
+// cnt0 (nullable, a ragged batch): the pair's own initial counts replace M0 + N0
 hipError_t stop_decide(const float* token, const int* cnt, int* act, int* stop, const SegLayout& L, float thr,
-                       float depth_conf, int layer, hipStream_t st);
+                       float depth_conf, int layer, hipStream_t st, const int* cnt0 = nullptr);
 // keep flags + in-segment exclusive scan (get_pruning_mask :586-593): running pairs keep
 // sigmoid(z) > width_thr or (token && token <= conf_thr); frozen pairs keep every point
 hipError_t prune_scan(const float* zmatch, const float* token, const int* cnt_in, int* cnt_out, const int* act,

@@ -351,6 +351,7 @@ struct Work {
   int rows_pad;
   size_t R;
   int *flags, *pos, *ind, *indb, *cnt, *cntb, *act, *stop;  // pruning / early stop (SegLayout)
+  int* cnt0;  // a ragged batch: the caller's counts, clamped (cnt shrinks with pruning, cnt0 does not)
   unsigned* rtab;  // PREC_H3 range table (kernels.h RangeOut), nslots slots
   int nslots;
   int64_t *m0c, *m1c;
@@ -401,6 +402,12 @@ Work carve(char* base, int B, int M, int N, bool prune, int din, int n_layers) {
   w.apart = w.apart_floats ? tf(w.apart_floats) : nullptr;
   w.nslots = range_slots(n_layers);
   w.rtab = reinterpret_cast<unsigned*>(ti((size_t)w.nslots * lg::kRangeStride));
+  // per-pair counts and state: a ragged batch needs them whether or not the config prunes
+  w.cnt = ti(2 * (size_t)B);
+  w.cntb = ti(2 * (size_t)B);
+  w.cnt0 = ti(2 * (size_t)B);
+  w.act = ti(B);
+  w.stop = ti(B);
   if (prune) {
     w.X2 = tf(R * D);
     w.cos2 = tf(R * 32);
@@ -409,10 +416,6 @@ Work carve(char* base, int B, int M, int N, bool prune, int din, int n_layers) {
     w.pos = ti(R);
     w.ind = ti(R);
     w.indb = ti(R);
-    w.cnt = ti(2 * (size_t)B);
-    w.cntb = ti(2 * (size_t)B);
-    w.act = ti(B);
-    w.stop = ti(B);
     w.m0c = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * B * M));
     w.m1c = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * B * N));
     w.s0c = tf((size_t)B * M);
@@ -706,6 +709,11 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   if ((out->layer_descriptors0 || out->layer_descriptors1) && (do_stop || do_prune))
     return fail(LG_E_INVALID, "layer_descriptors need early stop and pruning off (training-mode outputs)");
   if (do_prune && (!out->prune0 || !out->prune1)) return fail(LG_E_INVALID, "prune0/prune1 outputs required with pruning");
+  // a ragged batch: pair b has num_keypoints0[b] <= M and num_keypoints1[b] <= N real points, stored
+  // first; the rest of each slot is padding that nothing reads into a result
+  if ((in->num_keypoints0 == nullptr) != (in->num_keypoints1 == nullptr))
+    return fail(LG_E_INVALID, "num_keypoints0 and num_keypoints1 must be given together");
+  const bool ragged = in->num_keypoints0 != nullptr;
   const Work need = carve(nullptr, B, M0, N0, prune_enabled(c), c.input_dim, c.n_layers);
   const bool din_a16 = ((uintptr_t)in->descriptors0 % 16 == 0) && ((uintptr_t)in->descriptors1 % 16 == 0);
   if (!workspace || workspace_bytes < need.bytes)
@@ -776,6 +784,26 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   };
   if (prec == PREC_H3) LG_HIP(hipMemsetAsync(w.rtab, 0, (size_t)w.nslots * lg::kRangeStride * sizeof(unsigned), st));
   h->pass_started = true;
+  // ---- early stop / point pruning for any batch size, counts on the device (kernels.h
+  // SegLayout): each (image, pair) keeps a fixed slot whose kept points are a compacted prefix;
+  // GEMMs skip dead rows, the attention reads per-pair counts, a stopped pair is frozen.  A ragged
+  // batch starts from the caller's counts instead of the slot sizes and uses the same masks (with
+  // nothing else on, the counts never change and no pair is ever frozen)
+  const bool seg = do_stop || do_prune;
+  const bool counted = seg || ragged;
+  const SegLayout SL{B, M0, N0};
+  int* cnt = w.cnt;
+  int* cntb = w.cntb;
+  int* ind = w.ind;
+  int* indb = w.indb;
+  RowMask live{};  // cnt == null outside pruning / ragged batches: every row live
+  if (ragged) {
+    LG_HIP(prune_init_counts(SL, in->num_keypoints0, in->num_keypoints1, cnt, w.cnt0, w.act, w.stop, L,
+                             seg ? ind : nullptr, st));
+  } else if (seg) {
+    LG_HIP(prune_init(SL, cnt, w.act, w.stop, L, ind, st));
+  }
+  if (counted) live = RowMask{cnt, seg ? w.act : nullptr, 1, SL};
   int s_x = -1;  // slot of the current residual-stream plane image Xp
   // set when w.X was not initialised from the descriptors: layer 0's self-block ffn.3 reads its
   // residual rows from here (image 0 rows, then image 1 rows)
@@ -795,11 +823,16 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       }
       const int s_in = slot(), s_d = slot();
       s_x = slot();
-      LG_HIP(range_absmax2(d0, (size_t)B * M * din, d1, (size_t)B * N * din, rt, s_in, st));
-      LG_HIP(rows_to_planes(d0, B * M, din, din, w.Dp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_d), st));
-      LG_HIP(rows_to_planes(d1, B * N, din, din, w.Dp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_d), st));
+      if (ragged) {  // real rows only: the padding must not reach the range table
+        LG_HIP(range_absmax_rows(d0, B * M, din, din, 0, live, rt, s_in, st));
+        LG_HIP(range_absmax_rows(d1, B * N, din, din, B * M, live, rt, s_in, st));
+      } else {
+        LG_HIP(range_absmax2(d0, (size_t)B * M * din, d1, (size_t)B * N * din, rt, s_in, st));
+      }
+      LG_HIP(rows_to_planes(d0, B * M, din, din, w.Dp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_d), st, nullptr, &live));
+      LG_HIP(rows_to_planes(d1, B * N, din, din, w.Dp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_d), st, nullptr, &live));
       GemmH3Args g = gemm_h3_base();
-      g.A0 = image(w.Dp, din); g.K0 = din; g.K = din; wplanes(g, h->Wi); g.rtab = rt; g.a0_slot = s_d;
+      g.A0 = image(w.Dp, din); g.K0 = din; g.K = din; wplanes(g, h->Wi); g.rtab = rt; g.a0_slot = s_d; g.rm = live;
       g.bias = Wb + h->bi; g.R = B * (M + N); g.Nout = D; g.Y = w.X; g.ldy = D;
       g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP; g.ro = ro(s_d, h->gi, -1, 0.f, h->bi_max, s_x, 1);
       LG_HIP(gemmh(g, EPI_STORE));
@@ -815,13 +848,24 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   } else {
     const int s_in = prec == PREC_H3 ? slot() : -1;
     s_x = prec == PREC_H3 ? slot() : -1;
-    if (prec == PREC_H3) {
+    if (prec == PREC_H3 && ragged) {  // real rows only: the padding must not reach the range table
+      LG_HIP(range_absmax_rows(in->descriptors0, B * M, D, D, 0, live, rt, s_in, st));
+      LG_HIP(range_absmax_rows(in->descriptors1, B * N, D, D, B * M, live, rt, s_in, st));
+    } else if (prec == PREC_H3) {
       LG_HIP(range_absmax2(in->descriptors0, (size_t)B * M * D, in->descriptors1, (size_t)B * N * D, rt, s_in, st));
     }
     if (prec == PREC_H3 && din_a16 && L > 0) {
       // the plane image from one read of the descriptors; the fp32 residual stream w.X is first
       // written by layer 0's self-block ffn.3, which reads its residual from the descriptors
-      // themselves (res_in) -- no copy; with pruning / early stop every row of layer 0 is live
+      // themselves (res_in) -- no copy; with pruning / early stop every row of layer 0 is live.
+      // A ragged batch masks its padding from layer 0 on: ffn.3 reads the residual of live rows
+      // only, so padded rows of w.X are never written and nothing reads them
+      if (ragged) {
+        LG_HIP(rows_to_planes(in->descriptors0, B * M, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st, nullptr,
+                              &live));
+        LG_HIP(rows_to_planes(in->descriptors1, B * N, D, D, w.Xp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st,
+                              nullptr, &live));
+      } else {
 #if LG_MERGE_R2P
       LG_HIP(rows_to_planes2(in->descriptors0, B * M, in->descriptors1, B * N, D, D, w.Xp, RP, 0,
                              ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
@@ -829,12 +873,14 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       LG_HIP(rows_to_planes(in->descriptors0, B * M, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
       LG_HIP(rows_to_planes(in->descriptors1, B * N, D, D, w.Xp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
 #endif
+      }
       res_in0 = in->descriptors0;
       res_in1 = in->descriptors1;
     } else {
       LG_HIP(hipMemcpyAsync(w.X, in->descriptors0, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
       LG_HIP(hipMemcpyAsync(w.X + (size_t)B * M * D, in->descriptors1, sizeof(float) * B * N * D, hipMemcpyDeviceToDevice, st));
-      if (prec == PREC_H3) LG_HIP(rows_to_planes(w.X, B * (M + N), D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
+      if (prec == PREC_H3)
+        LG_HIP(rows_to_planes(w.X, B * (M + N), D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st, nullptr, &live));
     }
   }
 
@@ -842,13 +888,16 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   {
     const float* s0 = in->image_size0;
     const float* s1 = in->image_size1;
-    if (!s0) { LG_HIP(kpt_extent(in->keypoints0, B, M, w.size, st)); s0 = w.size; }
-    if (!s1) { LG_HIP(kpt_extent(in->keypoints1, B, N, w.size + 2 * B, st)); s1 = w.size + 2 * B; }
+    const int* pc0 = ragged ? cnt : nullptr;  // the pair's own counts: extent and condition
+    const int* pc1 = ragged ? cnt + B : nullptr;
+    if (!s0) { LG_HIP(kpt_extent(in->keypoints0, B, M, w.size, st, pc0)); s0 = w.size; }
+    if (!s1) { LG_HIP(kpt_extent(in->keypoints1, B, N, w.size + 2 * B, st, pc1)); s1 = w.size + 2 * B; }
     PEArgs p;
     p.Wr = Wb + h->Wr; p.Wc = Wb + h->Wc; p.bc = Wb + h->bc; p.m_in = c.add_scale_ori ? 4 : 2; p.B = B;
     p.kpts = in->keypoints0; p.size = s0; p.scales = in->scales0; p.oris = in->oris0; p.n = M;
-    p.cosb = w.cosb; p.sinb = w.sinb;
+    p.cosb = w.cosb; p.sinb = w.sinb; p.cnt = pc0;
     PEArgs p1 = p;
+    p1.cnt = pc1;
     p1.kpts = in->keypoints1; p1.size = s1; p1.scales = in->scales1; p1.oris = in->oris1; p1.n = N;
     p1.cosb = w.cosb + (size_t)B * M * 32; p1.sinb = w.sinb + (size_t)B * M * 32;
 #if LG_MERGE_PE
@@ -859,20 +908,6 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
 #endif
   }
 
-  // ---- early stop / point pruning for any batch size, counts on the device (kernels.h
-  // SegLayout): each (image, pair) keeps a fixed slot whose kept points are a compacted prefix;
-  // GEMMs skip dead rows, the attention reads per-pair counts, a stopped pair is frozen
-  const bool seg = do_stop || do_prune;
-  const SegLayout SL{B, M0, N0};
-  int* cnt = w.cnt;
-  int* cntb = w.cntb;
-  int* ind = w.ind;
-  int* indb = w.indb;
-  RowMask live{};  // cnt == null outside pruning: every row live
-  if (seg) {
-    LG_HIP(prune_init(SL, cnt, w.act, w.stop, L, ind, st));
-    live = RowMask{cnt, w.act, 1, SL};
-  }
   if (out->prune0) LG_HIP(fill_i64(out->prune0, do_prune ? 1 : L, (size_t)B * M0, st));
   if (out->prune1) LG_HIP(fill_i64(out->prune1, do_prune ? 1 : L, (size_t)B * N0, st));
 
@@ -883,7 +918,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool direct_out = prec == PREC_H3 && !seg && !do_stop && !do_prune && out->ref_descriptors0 &&
                           out->ref_descriptors1 && a16(out->ref_descriptors0) && a16(out->ref_descriptors1) &&
-                          !out->layer_descriptors0 && !out->layer_descriptors1;
+                          !out->layer_descriptors0 && !out->layer_descriptors1 &&
+                          (LG_MERGE_GEMV || !ragged);  // the two-call matchability masks by per-source rows
   for (int i = 0; i < L; ++i) {
     const LayerW& lw = h->layers[i];
     for (int blk = 0; blk < 2; ++blk) {
@@ -921,8 +957,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       const void* vp1 = static_cast<const char*>(w.VP) + 2 * img1;
       float* ctx1 = w.ctx + (size_t)B * M * D;
       // per-pair counts of a pruned batch: image 0 = cnt[0..B), image 1 = cnt[B..2B)
-      const int* c0 = seg ? cnt : nullptr;
-      const int* c1 = seg ? cnt + B : nullptr;
+      const int* c0 = counted ? cnt : nullptr;
+      const int* c1 = counted ? cnt + B : nullptr;
       const int* act = seg ? w.act : nullptr;
       if (blk == 0) {  // self: q/k/v of the same image, scale 1/sqrt(64) (SDPA default)
         a0 = {w.Q, w.KP, w.VP, ps, w.ctx, M, M, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c0, act};
@@ -1021,7 +1057,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
     const float thr_c = confidence_threshold(i, L);
     if (do_stop) {
       LG_HIP(gemv_256(w.X, Wb + lw.wt, Wb + lw.bt, w.tok, R, 1, st));
-      LG_HIP(stop_decide(w.tok, cnt, w.act, w.stop, SL, thr_c, (float)c.depth_confidence, i, st));
+      LG_HIP(stop_decide(w.tok, cnt, w.act, w.stop, SL, thr_c, (float)c.depth_confidence, i, st,
+                         ragged ? w.cnt0 : nullptr));
     }
     // ---- width pruning (lightglue.py:532-547, get_pruning_mask :586-593), compaction inside each
     // pair's slot; a pair that stopped at this layer keeps every point (the reference breaks first)
@@ -1098,7 +1135,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       if (rc != LG_OK) return rc;
     }
   } else {
-    const int rc = head(L - 1, seg ? RowMask{cnt, nullptr, 0, SL} : RowMask{});
+    const int rc = head(L - 1, counted ? RowMask{cnt, nullptr, 0, SL} : RowMask{});
     if (rc != LG_OK) return rc;
   }
   if (!fused_sim) {
@@ -1129,9 +1166,10 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   memset(&aa, 0, sizeof(aa));
   aa.sim = simbuf; aa.z0 = w.z; aa.z1 = w.z + (size_t)B * M; aa.la = out->log_assignment; aa.ws = w.aws;
   aa.B = B; aa.M = M; aa.N = N; aa.th = (float)c.filter_threshold;
-  if (seg) {  // per-pair kept counts; la holds pair b's [M_b+1][N_b+1] block at the capacity strides
+  if (counted) {  // per-pair kept counts; la holds pair b's [M_b+1][N_b+1] block at the capacity strides
     aa.Mb = cnt;
     aa.Nb = cnt + B;
+    aa.fixed = !seg;  // a ragged batch without pruning / early stop: the fixed-shape la (kernels.h)
   }
   if (do_prune) {
     aa.m0 = w.m0c; aa.m1 = w.m1c; aa.s0 = w.s0c; aa.s1 = w.s1c;
@@ -1149,6 +1187,9 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       LG_HIP(assign(aa));
     }
   }
+  if (ragged)  // padded points: matches -1, scores 0, prune 0
+    LG_HIP(ragged_pad_outputs(SL, w.cnt0, out->matches0, out->matches1, out->matching_scores0, out->matching_scores1,
+                              out->prune0, out->prune1, st));
   if (out->ref_descriptors0 && !direct_out)
     LG_HIP(hipMemcpyAsync(out->ref_descriptors0, w.X, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
   if (out->ref_descriptors1 && !direct_out)
@@ -1159,6 +1200,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   out->stop_layer = L - 1;
   out->kept0 = M;
   out->kept1 = N;
+  // a ragged batch without pruning / early stop stays asynchronous: the caller knows the counts
+  if (ragged && !seg && out->kept) LG_HIP(hipMemcpyAsync(out->kept, cnt, 2 * B * sizeof(int), hipMemcpyDeviceToDevice, st));
   if (seg) {
     if (out->kept) LG_HIP(hipMemcpyAsync(out->kept, cnt, 2 * B * sizeof(int), hipMemcpyDeviceToDevice, st));
     if (out->stop) LG_HIP(hipMemcpyAsync(out->stop, w.stop, B * sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -1169,7 +1212,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
     out->kept0 = hc[0];
     out->kept1 = hc[B];
     out->stop_layer = hc[2 * B];
-    for (int k = 0; k < 2 * B; ++k)
+    for (int k = 0; k < 2 * B && !ragged; ++k)  // (an empty pair of a ragged batch just has no matches)
       if (hc[k] == 0)  // the reference's filter_matches fails on the empty set the same way
         return fail(LG_E_INVALID, "max(): Expected reduction dim to have non-zero size (all keypoints pruned)");
   }

@@ -432,6 +432,8 @@ int lg_train_forward(lg_handle_t* h, const float* const* params, const lg_inputs
   if (int e = check_shape(h, in->B, in->M, in->N)) return e;
   if (!in->keypoints0 || !in->keypoints1 || !in->descriptors0 || !in->descriptors1)
     return fail(LG_E_INVALID, "null input tensor");
+  if (in->num_keypoints0 || in->num_keypoints1)
+    return fail(LG_E_INVALID, "num_keypoints0/1 (ragged batches) are not supported by the training kernels");
   const Dims d = dims_of(h, in->B, in->M, in->N);
   if (d.m_in == 4 && (!in->scales0 || !in->oris0 || !in->scales1 || !in->oris1))
     return fail(LG_E_INVALID, "add_scale_ori needs scales0/1 and oris0/1");

@@ -625,6 +625,15 @@ class LightGlue(nn.Module):
             assert key in data, f"Missing key {key} in data"
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
         device = kpts0.device
+        # a ragged batch (no reference counterpart): pair i has num_keypoints0[i] <= m real points in
+        # image 0 and num_keypoints1[i] <= n in image 1, stored first; the rest is padding.  Checked
+        # on the host, before any device work
+        nk0, nk1 = self._check_counts(data.get("num_keypoints0"), data.get("num_keypoints1"), kpts0.shape[0])
+        if nk0 is not None and self.training and torch.is_grad_enabled() and (
+                data["descriptors0"].requires_grad or data["descriptors1"].requires_grad
+                or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("lightglue_amd: num_keypoints0/1 (ragged batches) are not supported by the "
+                                      "training kernels; pad or batch equal counts")
         if device.type != "cuda":
             raise RuntimeError("lightglue_amd: inputs must be on a HIP (cuda) device; there is no CPU path")
         b, m, _ = kpts0.shape
@@ -656,12 +665,33 @@ class LightGlue(nn.Module):
         if self.training and torch.is_grad_enabled() and (
                 d0.requires_grad or d1.requires_grad or any(p.requires_grad for p in self.parameters())):
             return self._forward_train((k0, k1, s0, s1, sc0, o0, sc1, o1), d0, d1)
-        inputs = (k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1)
+        if nk0 is not None:  # any integer dtype, CPU or device -> int32 on the device
+            nk0 = nk0.to(device=device, dtype=torch.int32).contiguous()
+            nk1 = nk1.to(device=device, dtype=torch.int32).contiguous()
+        inputs = (k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1, nk0, nk1)
         pruning = (c.width_confidence > 0 or c.depth_confidence > 0) and not self.training
         if self._graphs is not None and not pruning and not self.training:
-            key = (str(device),) + tuple(None if t is None else tuple(t.shape) for t in inputs)
+            key = (str(device), nk0 is not None) + tuple(None if t is None else tuple(t.shape) for t in inputs)
             return self._graph_forward(inputs, key)
         return self._forward_native(*inputs)
+
+    @staticmethod
+    def _check_counts(nk0, nk1, b):
+        """Validate data["num_keypoints0/1"] (host-side checks only): both or neither, shape [B],
+        an integer dtype.  Returns them as tensors (wherever they live) or (None, None)."""
+        if nk0 is None and nk1 is None:
+            return None, None
+        if nk0 is None or nk1 is None:
+            raise ValueError("lightglue_amd: num_keypoints0 and num_keypoints1 must be given together")
+        out = []
+        for name, t in (("num_keypoints0", nk0), ("num_keypoints1", nk1)):
+            t = torch.as_tensor(t)
+            if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+                raise ValueError(f"lightglue_amd: {name} must have an integer dtype, got {t.dtype}")
+            if tuple(t.shape) != (b,):
+                raise ValueError(f"lightglue_amd: {name} must have shape [{b}], got {list(t.shape)}")
+            out.append(t)
+        return out[0], out[1]
 
     # ------------------------------------------------------------ training forward (autograd)
     def _schema_names(self):
@@ -727,7 +757,7 @@ class LightGlue(nn.Module):
             "stop_layer": torch.full((b,), L - 1, dtype=torch.int64),
         }
 
-    def _forward_native(self, k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1):
+    def _forward_native(self, k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1, nk0=None, nk1=None):
         """One lg_forward call on prepared (fp32, contiguous, on-device) inputs."""
         c = self.conf
         device = k0.device
@@ -757,7 +787,8 @@ class LightGlue(nn.Module):
         if self._ws is None or self._ws.numel() < ws_bytes.value or self._ws.device != device:
             self._ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=device)
         flags = _lib.LG_FWD_TRAINING_GATE if self.training else 0
-        inp = _lib.LGInputs(b, m, n, *[_ptr(t) for t in (k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1)], flags)
+        inp = _lib.LGInputs(b, m, n, *[_ptr(t) for t in (k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1)], flags,
+                            _ptr(nk0), _ptr(nk1))
         final, layers = (None, rd0) if self.training else (rd0, None)
         final1, layers1 = (None, rd1) if self.training else (rd1, None)
         kept = torch.empty((2, b), dtype=torch.int32, device=device) if pruning else None
@@ -791,6 +822,13 @@ class LightGlue(nn.Module):
         }
         if sim is not None:
             pred["similarity"] = sim
+        if nk0 is not None:  # echoed back; padded points have matches -1, scores 0, prune 0
+            pred["num_keypoints0"], pred["num_keypoints1"] = nk0, nk1
+            if not (c.width_confidence > 0 and not self.training):
+                ran = ((nk0 > 0) & (nk1 > 0))[:, None]  # a pair with an empty image runs nothing
+                prune0 = prune0 * ((torch.arange(m, device=device)[None] < nk0[:, None]) & ran)
+                prune1 = prune1 * ((torch.arange(n, device=device)[None] < nk1[:, None]) & ran)
+                pred["prune0"], pred["prune1"] = prune0, prune1
         if pruning:
             # kept points per pair (the library synchronised once to return them): the
             # reference's outputs cover the kept points only -- its log_assignment is

@@ -192,6 +192,22 @@ class SuperPoint(nn.Module):
             _lib.check(lib.sp_sample_descriptors(self._handle, _ptr(kp), _ptr(full), B, kp.shape[1], _ptr(desc), _ptr(ws),
                                                  nb, stream), "sp_sample_descriptors")
             out_pred = {"keypoints": kp + 0.5, "keypoint_scores": sc, "descriptors": desc[:, :kp.shape[1]]}
+        elif data.get("ragged_keypoints"):
+            # opt-in per call (no reference counterpart): unequal counts come back as a ragged batch,
+            # [B, max count, ...] with zero padding and the per-image counts the kernel filled on the
+            # device (the matcher's num_keypoints0/1); no sync beyond the host counts above
+            k = n_max
+            if desc is None:  # every keypoint kept: sample now that the counts are known
+                desc = torch.empty((B, k, 256), device=device)
+                kp = (kpts[:, :k] - 0.5).contiguous()
+                _lib.check(lib.sp_sample_descriptors(self._handle, _ptr(kp), _ptr(counts), B, k, _ptr(desc), _ptr(ws), nb,
+                                                     stream), "sp_sample_descriptors")
+            real = torch.arange(k, device=device)[None] < counts[:, None]
+            zero = torch.zeros((), device=device)
+            out_pred = {"keypoints": torch.where(real[..., None], kpts[:, :k], zero),
+                        "keypoint_scores": torch.where(real, scores[:, :k], zero),
+                        "descriptors": torch.where(real[..., None], desc[:, :k], zero),
+                        "num_keypoints": counts}
         else:
             if len(set(n)) != 1:
                 raise RuntimeError(f"stack expects each tensor to be equal size, but got keypoint counts {n} "

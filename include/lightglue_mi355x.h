@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LG_ABI_VERSION 10
+#define LG_ABI_VERSION 11
 
 enum {
   LG_OK = 0,
@@ -86,6 +86,19 @@ typedef struct {
   const float* scales1;         /* device [B,N] */
   const float* oris1;           /* device [B,N] */
   int32_t flags;                /* OR of LG_FWD_*: per-call options (no reference counterpart) */
+  /* ABI 11 -- a ragged batch (no reference counterpart): pair b has num_keypoints0[b] <= M real
+   * points in image 0 and num_keypoints1[b] <= N in image 1, stored first; the rest of each slot is
+   * padding whose contents are arbitrary (NaN included) and never reach a result.  Pair b then
+   * gives what it gives alone at M = num_keypoints0[b], N = num_keypoints1[b].  Both NULL (a
+   * zeroed struct): every slot is full.  Give both or neither.  The counts are clamped to
+   * [0, capacity] on the device and never read on the host; a pair with an empty image has no
+   * matches.  Padded points: matches -1, scores 0, prune 0.  Without pruning / early stop the
+   * forward stays asynchronous and log_assignment keeps its [B,M+1,N+1] shape: pair b's real block
+   * at i < n0, j < n1, the dustbin column at N (i < n0), the dustbin row at M (j < n1), [M,N] = 0,
+   * every other entry -inf.  With pruning / early stop the kept-block convention of `kept` holds.
+   * Not supported by lg_train_forward / lg_train_backward. */
+  const int32_t* num_keypoints0; /* device [B] or NULL */
+  const int32_t* num_keypoints1; /* device [B] or NULL */
 } lg_inputs_t;
 
 /* lg_inputs_t.flags
