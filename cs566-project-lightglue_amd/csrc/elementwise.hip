@@ -45,43 +45,7 @@ __global__ void kpt_extent_kernel(const float* kpts, int n, float* size_out, con
   if (threadIdx.x < 2) size_out[b * 2 + threadIdx.x] = add_rn(1.f, sub_rn(red[threadIdx.x][0], red[2 + threadIdx.x][0]));
 }
 
-__global__ void pe_kernel(PEArgs a) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;  // (point, freq)
-  const int f = gid & 31;
-  const int pt = gid >> 5;
-  if (pt >= a.B * a.n) return;
-  const int b = pt / a.n;
-  int nc = a.n;  // the condition: the pair's own keypoint count
-  if (a.cnt) {
-    nc = a.cnt[b];
-    if (pt - b * a.n >= nc) return;  // padding of a ragged batch
-  }
-  const float w = a.size[b * 2 + 0], h = a.size[b * 2 + 1];
-  const float scale = div_rn(fmaxf(w, h), 2.f);
-  float x[4];
-  x[0] = div_rn(sub_rn(a.kpts[(size_t)pt * 2 + 0], div_rn(w, 2.f)), scale);
-  x[1] = div_rn(sub_rn(a.kpts[(size_t)pt * 2 + 1], div_rn(h, 2.f)), scale);
-  if (a.m_in == 4) {
-    x[2] = a.scales[pt];
-    x[3] = a.oris[pt];
-  }
-  const float* wr = a.Wr + f * a.m_in;
-  float p = mul_rn(x[0], wr[0]);
-  for (int k = 1; k < a.m_in; ++k) p = __fmaf_rn(x[k], wr[k], p);
-  const float cond = add_rn(mul_rn((float)nc, a.Wc[f]), a.bc[f]);  // relu(n) = n
-  p = add_rn(p, cond);
-  a.cosb[(size_t)pt * kFreq + f] = cosf(p);
-  a.sinb[(size_t)pt * kFreq + f] = sinf(p);
-}
-
-hipError_t positional_encoding(const PEArgs& a0, hipStream_t st) {
-  if (a0.B * a0.n == 0) return hipSuccess;
-  const int threads = a0.B * a0.n * 32;
-  hipLaunchKernelGGL(pe_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, a0);
-  return hipGetLastError();
-}
-
-// both images in one launch (blockIdx.y selects the image; the values are pe_kernel's)
+// both images in one launch (blockIdx.y selects the image)
 __global__ void pe2_kernel(PEArgs a0, PEArgs a1) {
   const PEArgs& a = blockIdx.y == 0 ? a0 : a1;
   if ((int)blockIdx.x * (int)blockDim.x >= a.B * a.n * 32) return;

@@ -223,7 +223,6 @@ struct PEArgs {
   const int* cnt;      // [B] or null: per-pair counts of a ragged batch -- the condition is the pair's
                        // own count (not the capacity n) and padded points are skipped
 };
-hipError_t positional_encoding(const PEArgs& a, hipStream_t st);
 // both images in one launch
 hipError_t positional_encoding2(const PEArgs& a0, const PEArgs& a1, hipStream_t st);
 // size = 1 + max - min of each pair's keypoints (normalize_keypoints fallback, lightglue.py:25-26)

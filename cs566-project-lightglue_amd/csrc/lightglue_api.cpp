@@ -14,16 +14,6 @@
 #include "../../include/lightglue_mi355x.h"
 #include "kernels.h"
 
-// two-image launches of the input preparation / final matchability (round 6 A/B switches)
-#ifndef LG_MERGE_PE
-#define LG_MERGE_PE 1
-#endif
-#ifndef LG_MERGE_R2P
-#define LG_MERGE_R2P 1
-#endif
-#ifndef LG_MERGE_GEMV
-#define LG_MERGE_GEMV 1
-#endif
 #include "common.h"
 
 namespace {
@@ -865,14 +855,9 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
                               &live));
         LG_HIP(rows_to_planes(in->descriptors1, B * N, D, D, w.Xp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st,
                               nullptr, &live));
-      } else {
-#if LG_MERGE_R2P
-      LG_HIP(rows_to_planes2(in->descriptors0, B * M, in->descriptors1, B * N, D, D, w.Xp, RP, 0,
-                             ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
-#else
-      LG_HIP(rows_to_planes(in->descriptors0, B * M, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
-      LG_HIP(rows_to_planes(in->descriptors1, B * N, D, D, w.Xp, RP, B * M, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
-#endif
+      } else {  // both images in one launch
+        LG_HIP(rows_to_planes2(in->descriptors0, B * M, in->descriptors1, B * N, D, D, w.Xp, RP, 0,
+                               ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
       }
       res_in0 = in->descriptors0;
       res_in1 = in->descriptors1;
@@ -900,12 +885,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
     p1.cnt = pc1;
     p1.kpts = in->keypoints1; p1.size = s1; p1.scales = in->scales1; p1.oris = in->oris1; p1.n = N;
     p1.cosb = w.cosb + (size_t)B * M * 32; p1.sinb = w.sinb + (size_t)B * M * 32;
-#if LG_MERGE_PE
-    LG_HIP(positional_encoding2(p, p1, st));
-#else
-    LG_HIP(positional_encoding(p, st));
-    LG_HIP(positional_encoding(p1, st));
-#endif
+    LG_HIP(positional_encoding2(p, p1, st));  // both images in one launch
   }
 
   if (out->prune0) LG_HIP(fill_i64(out->prune0, do_prune ? 1 : L, (size_t)B * M0, st));
@@ -918,8 +898,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool direct_out = prec == PREC_H3 && !seg && !do_stop && !do_prune && out->ref_descriptors0 &&
                           out->ref_descriptors1 && a16(out->ref_descriptors0) && a16(out->ref_descriptors1) &&
-                          !out->layer_descriptors0 && !out->layer_descriptors1 &&
-                          (LG_MERGE_GEMV || !ragged);  // the two-call matchability masks by per-source rows
+                          !out->layer_descriptors0 && !out->layer_descriptors1;
   for (int i = 0; i < L; ++i) {
     const LayerW& lw = h->layers[i];
     for (int blk = 0; blk < 2; ++blk) {
@@ -1117,13 +1096,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       LG_HIP(gemm(g, EPI_STORE, 1));
     }
     if (direct_out) {  // the final fp32 descriptors live in the outputs (every row live)
-#if LG_MERGE_GEMV
       LG_HIP(gemv_256_masked2(out->ref_descriptors0, B * M, out->ref_descriptors1, B * N, Wb + la.wm, Wb + la.bm, w.z, m,
                               st));
-#else
-      LG_HIP(gemv_256_masked(out->ref_descriptors0, Wb + la.wm, Wb + la.bm, w.z, B * M, m, st));
-      LG_HIP(gemv_256_masked(out->ref_descriptors1, Wb + la.wm, Wb + la.bm, w.z + (size_t)B * M, B * N, m, st));
-#endif
     } else {
       LG_HIP(gemv_256_masked(w.X, Wb + la.wm, Wb + la.bm, w.z, R, m, st));
     }

@@ -6,7 +6,6 @@
 // Row space: R = B (M + N) rows of 256 -- image-0 rows (pair-major, R0 = B M of them) then image-1
 // rows -- as in the eval forward.  Every activation is row-major fp32; head h of a projection is
 // columns [64h, 64h + 64).
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,32 +23,6 @@ int handle_device(const lg_handle* h);
 void handle_grad_ready(const lg_handle* h, int layer, void* stream);  // lg_set_grad_ready_hook
 int handle_weight_index(const lg_handle* h, const std::string& name);
 }  // namespace lg
-
-#ifndef LG_HEAD_SIM_X6
-#define LG_HEAD_SIM_X6 1  // the heads' similarity md0 md1^T on the bf16x6 GEMM (env LG_HEAD_SIM_X6 overrides)
-#endif
-static bool head_sim_x6() {
-  static const int v = [] {
-    const char* e = getenv("LG_HEAD_SIM_X6");
-    return e ? atoi(e) : LG_HEAD_SIM_X6;
-  }();
-  return v != 0;
-}
-#ifndef LG_HEAD_X6
-#define LG_HEAD_X6 1  // 1: the assignment heads' products may take the bf16x6 GEMM too
-#endif
-#ifndef LG_HEAD_GMD_X6
-// 1: the heads' d(md0) = d(sim) md1 on the bf16x6 GEMM through md1^T (a batched transpose into
-// the d(md1) slot, which that product has not written yet); 0: the f32 MFMA kernel on md1 as is
-#define LG_HEAD_GMD_X6 1
-#endif
-static bool head_gmd_x6() {
-  static const int v = [] {
-    const char* e = getenv("LG_HEAD_GMD_X6");
-    return e ? atoi(e) : LG_HEAD_GMD_X6;
-  }();
-  return v != 0;
-}
 
 namespace {
 
@@ -221,14 +194,13 @@ struct Ctx {
   float* ws;
   size_t ws_floats;
   float* part;
-  bool x6 = true;  // the trunk's linears may take the bf16x6 GEMM; the heads follow LG_HEAD_X6
 };
 
 // y[M,N] = alpha (x[M,K] W[N,K]^T + b) + beta y
 hipError_t linear(const Ctx& c, const float* x, long long ldx, int rows, int K, const float* W, const float* b, int N,
                   float* y, long long ldy, float beta = 0.f, float alpha = 1.f) {
   TGemm g{x, W, y, ldx, K, ldy, 0, 0, 0, rows, N, K, 1, alpha, beta, b};
-  return tgemm(g, false, true, c.ws, c.ws_floats, c.st, c.x6);
+  return tgemm(g, false, true, c.ws, c.ws_floats, c.st);
 }
 // y[M,N] = res[M,N] + x[M,K] W[N,K]^T + b (the residual read in the epilogue, not copied into y first)
 hipError_t linear_res(const Ctx& c, const float* x, long long ldx, int rows, int K, const float* W, const float* b, int N,
@@ -236,24 +208,21 @@ hipError_t linear_res(const Ctx& c, const float* x, long long ldx, int rows, int
   TGemm g{x, W, y, ldx, K, ldy, 0, 0, 0, rows, N, K, 1, 1.f, 1.f, b};
   g.R = res;
   g.ldr = ldres;
-  return tgemm(g, false, true, c.ws, c.ws_floats, c.st, c.x6);
+  return tgemm(g, false, true, c.ws, c.ws_floats, c.st);
 }
 // dx[M,K] (+)= dy[M,N] W[N,K]
 hipError_t linear_dgrad(const Ctx& c, const float* dy, long long lddy, int rows, int N, const float* W, int K, float* dx,
                         long long lddx, float beta = 0.f) {
   TGemm g{dy, W, dx, lddy, K, lddx, 0, 0, 0, rows, K, N, 1, 1.f, beta, nullptr};
-  return tgemm(g, false, false, c.ws, c.ws_floats, c.st, c.x6);
+  return tgemm(g, false, false, c.ws, c.ws_floats, c.st);
 }
 // dW[N,K] = dy[rows,N]^T x[rows,K]; db[N] = colsum(dy)
 hipError_t linear_wgrad(const Ctx& c, const float* dy, long long lddy, const float* x, long long ldx, int rows, int N,
                         int K, float* dW, float* db) {
   if (dW) {
     TGemm g{dy, x, dW, lddy, ldx, K, 0, 0, 0, N, K, rows, 1, 1.f, 0.f, nullptr};
-    // the bias gradient from the weight gradient's own read of dy when the kernel can (bf16x6 route)
-    const bool fused = db && c.x6 && tgemm_fuses_colsum(true, false);
-    if (fused) g.colsumA = db;
-    hipError_t e = tgemm(g, true, false, c.ws, c.ws_floats, c.st, c.x6);
-    if (e != hipSuccess || fused) return e;
+    g.colsumA = db;  // the bias gradient from the weight gradient's own read of dy
+    return tgemm(g, true, false, c.ws, c.ws_floats, c.st);
   }
   if (db) return colsum(dy, lddy, rows, N, nullptr, c.part, db, c.st);
   return hipSuccess;
@@ -276,43 +245,18 @@ TAttn attn_args(const float* Q, const float* K, const float* V, float* O, float*
   return a;
 }
 
-// ffn.0's input [X | message] read from its two halves (X where it lies, the message in CAT[:, 256:])
-// by the bf16x6 products of the forward and of the weight gradient, so X is never copied into
-// CAT[:, :256]; without those routes (A/B switches) the halves are copied together as before
-bool head_vec_fused() {  // env LG_HEAD_VEC_FUSED=0: the heads' 1-wide linears' gradients by four column sums
-  static const int v = [] {
-    const char* e = getenv("LG_HEAD_VEC_FUSED");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0;
-}
-
-bool ffn_two_source(const Ctx& c) {
-  static const int v = [] {
-    const char* e = getenv("LG_FFN_TWO_SOURCE");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0 && tgemm_two_source(c.x6 ? 1 : 0);
-}
-
-// FFN + residual of a block (lightglue.py:171-176,191,246-248): CAT[:, 256:] holds the message
+// FFN + residual of a block (lightglue.py:171-176,191,246-248): CAT[:, 256:] holds the message.
+// ffn.0's input [X | message] is read from its two halves (X where it lies, the message in
+// CAT[:, 256:]) by the bf16x6 products of the forward and of the weight gradient, so X is never
+// copied into CAT[:, :256]
 hipError_t ffn_forward(const Ctx& c, const Params& P, const std::string& pre, const float* X, Blk& b, int R) {
   hipError_t e;
-  if (ffn_two_source(c)) {
-    TGemm g{X, P.w(pre + ".ffn.0.weight"), b.H1, D, 2 * D, 2 * D, 0, 0, 0, R, 2 * D, 2 * D, 1, 1.f, 0.f,
-            P.w(pre + ".ffn.0.bias")};
-    g.A1 = b.CAT + D;
-    g.lda1 = 2 * D;
-    g.K0 = D;
-    if ((e = tgemm(g, false, true, c.ws, c.ws_floats, c.st, c.x6)) != hipSuccess) return e;
-  } else {
-    if ((e = hipMemcpy2DAsync(b.CAT, 2 * D * sizeof(float), X, D * sizeof(float), D * sizeof(float), R,
-                              hipMemcpyDeviceToDevice, c.st)) != hipSuccess)
-      return e;
-    if ((e = linear(c, b.CAT, 2 * D, R, 2 * D, P.w(pre + ".ffn.0.weight"), P.w(pre + ".ffn.0.bias"), 2 * D, b.H1, 2 * D)) !=
-        hipSuccess)
-      return e;
-  }
+  TGemm g{X, P.w(pre + ".ffn.0.weight"), b.H1, D, 2 * D, 2 * D, 0, 0, 0, R, 2 * D, 2 * D, 1, 1.f, 0.f,
+          P.w(pre + ".ffn.0.bias")};
+  g.A1 = b.CAT + D;
+  g.lda1 = 2 * D;
+  g.K0 = D;
+  if ((e = tgemm(g, false, true, c.ws, c.ws_floats, c.st)) != hipSuccess) return e;
   if ((e = lngelu_fwd(b.H1, P.w(pre + ".ffn.1.weight"), P.w(pre + ".ffn.1.bias"), R, b.G, b.ST, c.st)) != hipSuccess) return e;
   return linear_res(c, b.G, 2 * D, R, 2 * D, P.w(pre + ".ffn.3.weight"), P.w(pre + ".ffn.3.bias"), D, b.Y, D, X, D);
 }
@@ -329,23 +273,16 @@ hipError_t ffn_backward(const Ctx& c, const Params& P, const std::string& pre, c
   if ((e = lngelu_bwd(s.GG, b.H1, b.ST, P.w(pre + ".ffn.1.weight"), P.w(pre + ".ffn.1.bias"), R, s.GH, s.PART,
                       P.gr(pre + ".ffn.1.weight"), P.gr(pre + ".ffn.1.bias"), c.st)) != hipSuccess)
     return e;
-  if (ffn_two_source(c)) {
-    float* dW = P.gr(pre + ".ffn.0.weight");
-    float* db = P.gr(pre + ".ffn.0.bias");
-    if (dW) {  // dW = GH^T [X | message]: columns < 256 from X, the rest from CAT[:, 256:]
-      TGemm g{s.GH, X, dW, 2 * D, D, 2 * D, 0, 0, 0, 2 * D, 2 * D, R, 1, 1.f, 0.f, nullptr};
-      g.B1 = b.CAT + D;
-      g.ldb1 = 2 * D;
-      g.N0 = D;
-      const bool fused = db && tgemm_fuses_colsum(true, false);
-      if (fused) g.colsumA = db;
-      if ((e = tgemm(g, true, false, c.ws, c.ws_floats, c.st, c.x6)) != hipSuccess) return e;
-      if (db && !fused && (e = colsum(s.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st)) != hipSuccess) return e;
-    } else if (db && (e = colsum(s.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st)) != hipSuccess) {
-      return e;
-    }
-  } else if ((e = linear_wgrad(c, s.GH, 2 * D, b.CAT, 2 * D, R, 2 * D, 2 * D, P.gr(pre + ".ffn.0.weight"),
-                               P.gr(pre + ".ffn.0.bias"))) != hipSuccess) {
+  float* dW = P.gr(pre + ".ffn.0.weight");
+  float* db = P.gr(pre + ".ffn.0.bias");
+  if (dW) {  // dW = GH^T [X | message]: columns < 256 from X, the rest from CAT[:, 256:]
+    TGemm g{s.GH, X, dW, 2 * D, D, 2 * D, 0, 0, 0, 2 * D, 2 * D, R, 1, 1.f, 0.f, nullptr};
+    g.B1 = b.CAT + D;
+    g.ldb1 = 2 * D;
+    g.N0 = D;
+    g.colsumA = db;
+    if ((e = tgemm(g, true, false, c.ws, c.ws_floats, c.st)) != hipSuccess) return e;
+  } else if (db && (e = colsum(s.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st)) != hipSuccess) {
     return e;
   }
   if ((e = linear_dgrad(c, s.GH, 2 * D, R, 2 * D, P.w(pre + ".ffn.0.weight"), 2 * D, s.GC, 2 * D)) != hipSuccess) return e;
@@ -675,7 +612,7 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
   TR_HIP(hipSetDevice(handle_device(h)));
-  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART, LG_HEAD_X6 != 0};
+  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, grads};
   const std::string a = "log_assignment." + std::to_string(layer);
   const int R0 = B * M, R = B * (M + N);
@@ -689,7 +626,7 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
     TR_HIP(linear(c, s.X, D, R, D, Wf, P.w(a + ".final_proj.bias"), D, s.MD, D, 0.f, 0.25f));
     TR_HIP(gemv256(s.X, R, wm, P.w(a + ".matchability.bias"), s.Z, c.st));
     TGemm g{s.MD, s.MD + o1, s.SIM, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st, head_sim_x6() ? 2 : (int)c.x6));
+    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
     TR_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
   }
   // sigmoid_log_double_softmax backward (:284-296)
@@ -702,18 +639,18 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
   }
   TR_HIP(la_grad_z(s.Z, s.RS, s.GD, R, s.GZ, c.st));
   // d/d(final_proj output) = d/d(md) / 4: gmd0 = gsim md1, gmd1 = gsim^T md0
-  if (c.x6 && head_gmd_x6() && N % 16 == 0) {
+  if (N % 16 == 0) {  // gmd0 on the bf16x6 GEMM through md1^T; the f32 MFMA kernel on md1 as is otherwise
     float* md1t = s.GMD + o1;  // [B][D][N]: free until the d(md1) product below
     TR_HIP(transpose_batched(s.MD + o1, N, D, B, md1t, c.st));
     TGemm g{s.SIM, md1t, s.GMD, N, N, D, (long long)M * N, (long long)D * N, (long long)M * D, M, D, N, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st, 2));
+    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   } else {
     TGemm g{s.SIM, s.MD + o1, s.GMD, N, D, D, (long long)M * N, (long long)N * D, (long long)M * D, M, D, N, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st, c.x6));
+    TR_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st));
   }
   {
     TGemm g{s.SIM, s.MD, s.GMD + o1, N, D, D, (long long)M * N, (long long)M * D, (long long)N * D, N, D, M, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st, c.x6));
+    TR_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
   }
   TR_HIP(linear_wgrad(c, s.GMD, D, s.X, D, R, D, D, P.gr(a + ".final_proj.weight"), P.gr(a + ".final_proj.bias")));
   const bool tok = grad_token0 || grad_token1;
@@ -724,18 +661,11 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
     else TR_HIP(hipMemsetAsync(s.GT + R0, 0, (size_t)(R - R0) * 4, c.st));
   }
   const std::string t = "token_confidence." + std::to_string(layer) + ".token.0";
-  if (head_vec_fused()) {  // matchability's and the token linear's gradients in one read of X
-    TR_HIP(head_vec_grads(s.X, R, s.GZ, tok ? s.GT : nullptr, c.part, P.gr(a + ".matchability.weight"),
-                          P.gr(a + ".matchability.bias"), tok ? P.gr(t + ".weight") : nullptr,
-                          tok ? P.gr(t + ".bias") : nullptr, c.st));
-  } else {
-    if (float* g = P.gr(a + ".matchability.weight")) TR_HIP(colsum(s.X, D, R, D, s.GZ, c.part, g, c.st));
-    if (float* g = P.gr(a + ".matchability.bias")) TR_HIP(colsum(s.GZ, 1, R, 1, nullptr, c.part, g, c.st));
-    if (tok) {  // TokenConfidence (:108-122): logits = token(desc.detach()) -> the token Linear only
-      if (float* g = P.gr(t + ".weight")) TR_HIP(colsum(s.X, D, R, D, s.GT, c.part, g, c.st));
-      if (float* g = P.gr(t + ".bias")) TR_HIP(colsum(s.GT, 1, R, 1, nullptr, c.part, g, c.st));
-    }
-  }
+  // matchability's and the token linear's gradients in one read of X (TokenConfidence, :108-122:
+  // logits = token(desc.detach()) -> the token Linear only)
+  TR_HIP(head_vec_grads(s.X, R, s.GZ, tok ? s.GT : nullptr, c.part, P.gr(a + ".matchability.weight"),
+                        P.gr(a + ".matchability.bias"), tok ? P.gr(t + ".weight") : nullptr,
+                        tok ? P.gr(t + ".bias") : nullptr, c.st));
   if (grad_desc0) {
     TR_HIP(linear_dgrad(c, s.GMD, D, R0, D, Wf, D, grad_desc0, D));
     TR_HIP(rank1_add256(grad_desc0, R0, s.GZ, wm, c.st));
@@ -800,7 +730,7 @@ int lg_head_nll_forward(lg_handle_t* h, const float* const* params, int32_t laye
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
   TR_HIP(hipSetDevice(handle_device(h)));
-  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART, LG_HEAD_X6 != 0};
+  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, nullptr};
   const std::string a = "log_assignment." + std::to_string(layer);
   const int R0 = B * M, R = B * (M + N);
@@ -815,7 +745,7 @@ int lg_head_nll_forward(lg_handle_t* h, const float* const* params, int32_t laye
   }
   {
     TGemm g{s.MD, s.MD + o1, s.SIM, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st, head_sim_x6() ? 2 : (int)c.x6));
+    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   }
   TR_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
   TR_HIP(la_nll(s.SIM, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, gt_assignment, gt_matches0, gt_matches1, mode, balancing, out,
@@ -841,7 +771,7 @@ int lg_head_forward(lg_handle_t* h, const float* const* params, int32_t layer, c
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
   TR_HIP(hipSetDevice(handle_device(h)));
-  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART, LG_HEAD_X6 != 0};
+  const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, nullptr};
   const std::string a = "log_assignment." + std::to_string(layer);
   const int R0 = B * M, R = B * (M + N);
@@ -859,7 +789,7 @@ int lg_head_forward(lg_handle_t* h, const float* const* params, int32_t layer, c
   }
   {
     TGemm g{s.MD, s.MD + o1, sim, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st, head_sim_x6() ? 2 : (int)c.x6));
+    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   }
   TR_HIP(sim_lse(sim, B, M, N, s.LSER, s.LSEC, c.part, c.st));
   TR_HIP(la_forward(sim, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, log_assignment, c.st));

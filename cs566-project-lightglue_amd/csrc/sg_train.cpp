@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -206,8 +205,7 @@ struct Ctx {
   float* part;
 };
 
-#ifndef SG_TG_X6_FWD
-// SuperGlue's forward products (x W^T, the cost) on bf16x6; env SG_TG_X6_FWD overrides.  Round 5:
+// SuperGlue's forward products (x W^T, the cost) run on bf16x6 like every other tgemm product.  Round 5:
 // the realistic-size golden (sgtrain_b1_n512: 18 layers, 50 Sinkhorn iterations, 512 x 512) first
 // failed on this route (405x the bar on the descriptor gradient); the cause was one ReLU unit whose
 // float64 pre-activation is 2.5e-7 from the kink, which this forward puts on the other side -- its
@@ -215,32 +213,12 @@ struct Ctx {
 // evaluate the float64 oracle on this forward's own ReLU decisions and require every differing
 // decision to sit within 1e-4 of the kink: worst 0.984 of the bar with 2 such units, 0.970 on f32;
 // step 229.2 -> 214.1 ms (profiles/r05/sg_kink)
-#define SG_TG_X6_FWD 1
-#endif
-int fwd_x6() {
-  static const int v = [] {
-    const char* e = getenv("SG_TG_X6_FWD");
-    return e ? atoi(e) : SG_TG_X6_FWD;
-  }();
-  return v ? 2 : 0;  // 0: f32 MFMA whatever LightGlue's LG_TG_X6_FWD says (these are forward products only)
-}
-
-// mlp.0's input cat([x, message]) read from its two halves (x where it lies, the message in
-// CAT[:, 256:]) by the bf16x6 forward product and weight gradient: x is never copied into
-// CAT[:, :256] (env SG_MLP_TWO_SOURCE=0, or routes off: the copy as before)
-bool mlp_two_source() {
-  static const int v = [] {
-    const char* e = getenv("SG_MLP_TWO_SOURCE");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0 && tgemm_two_source(fwd_x6());
-}
 
 // y[rows,N] = alpha (x[rows,K] W[N,K]^T + b) + beta y
 hipError_t linear(const Ctx& c, const float* x, long long ldx, int rows, int K, const float* W, const float* b, int N,
                   float* y, long long ldy, float beta = 0.f) {
   TGemm g{x, W, y, ldx, K, ldy, 0, 0, 0, rows, N, K, 1, 1.f, beta, b};
-  return tgemm(g, false, true, c.ws, c.ws_floats, c.st, fwd_x6());
+  return tgemm(g, false, true, c.ws, c.ws_floats, c.st);
 }
 // y[rows,N] = res[rows,N] + x W^T + b (the residual read in the epilogue)
 hipError_t linear_res(const Ctx& c, const float* x, long long ldx, int rows, int K, const float* W, const float* b, int N,
@@ -248,7 +226,7 @@ hipError_t linear_res(const Ctx& c, const float* x, long long ldx, int rows, int
   TGemm g{x, W, y, ldx, K, ldy, 0, 0, 0, rows, N, K, 1, 1.f, 1.f, b};
   g.R = res;
   g.ldr = ldres;
-  return tgemm(g, false, true, c.ws, c.ws_floats, c.st, fwd_x6());
+  return tgemm(g, false, true, c.ws, c.ws_floats, c.st);
 }
 // dx[rows,K] (+)= dy[rows,N] W[N,K]
 hipError_t linear_dgrad(const Ctx& c, const float* dy, long long lddy, int rows, int N, const float* W, int K, float* dx,
@@ -261,11 +239,8 @@ hipError_t linear_wgrad(const Ctx& c, const float* dy, long long lddy, const flo
                         float* dW, float* db) {
   if (dW) {
     TGemm g{dy, x, dW, lddy, ldx, K, 0, 0, 0, N, K, rows, 1, 1.f, 0.f, nullptr};
-    // the bias gradient from the weight gradient's own read of dy when the kernel can (bf16x6 route)
-    const bool fused = db && tgemm_fuses_colsum(true, false);
-    if (fused) g.colsumA = db;
-    hipError_t e = tgemm(g, true, false, c.ws, c.ws_floats, c.st);
-    if (e != hipSuccess || fused) return e;
+    g.colsumA = db;  // the bias gradient from the weight gradient's own read of dy
+    return tgemm(g, true, false, c.ws, c.ws_floats, c.st);
   }
   if (db) return colsum(dy, lddy, rows, N, nullptr, c.part, db, c.st);
   return hipSuccess;
@@ -411,16 +386,14 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
     ST_HIP(tattn_forward(attn_args(y.QKV, o1, cross ? 0 : o1, y.O, y.LSE + lse1, B, N, cross ? M : N), c.st));
     // mlp(cat([x, merge(message)])) (:125-127,135-139) with batch-statistics BatchNorm per image set
     ST_HIP(linear(c, y.O, D, R, D, y.WM, P.w(p + ".attn.merge.bias"), D, y.CAT + D, 2 * D));
-    if (mlp_two_source()) {
+    {  // mlp.0's input cat([x, message]) read from its two halves (x where it lies, the message in
+       // CAT[:, 256:]) by the bf16x6 forward product and weight gradient: x is never copied into CAT[:, :256]
       TGemm g{X, P.w(p + ".mlp.0.weight"), y.H1, D, 2 * D, 2 * D, 0, 0, 0, R, 2 * D, 2 * D, 1, 1.f, 0.f,
               P.w(p + ".mlp.0.bias")};
       g.A1 = y.CAT + D;
       g.lda1 = 2 * D;
       g.K0 = D;
-      ST_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st, fwd_x6()));
-    } else {
-      ST_HIP(hipMemcpy2DAsync(y.CAT, 2 * D * 4, X, D * 4, D * 4, R, hipMemcpyDeviceToDevice, c.st));
-      ST_HIP(linear(c, y.CAT, 2 * D, R, 2 * D, P.w(p + ".mlp.0.weight"), P.w(p + ".mlp.0.bias"), 2 * D, y.H1, 2 * D));
+      ST_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
     }
     ST_HIP(bn_train_fwd_sets(y.H1, 2 * D, rows_of, 2 * D, P.w(p + ".mlp.1.weight"), P.w(p + ".mlp.1.bias"), y.G, 2 * D,
                              y.ST, c.part, sg_handle_sync(h), c.st));
@@ -439,7 +412,7 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
   {
     TGemm g{s.MD, s.MD + o1 * D, s.COST, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B,
             1.f / 16.f, 0.f, nullptr};
-    ST_HIP(tgemm(g, false, true, nullptr, 0, c.st, fwd_x6()));
+    ST_HIP(tgemm(g, false, true, nullptr, 0, c.st));
   }
   if (out->sinkhorn_cost)
     ST_HIP(hipMemcpyAsync(out->sinkhorn_cost, s.COST, (size_t)B * M * N * 4, hipMemcpyDeviceToDevice, c.st));
@@ -507,22 +480,19 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
     for (int set = 0; set < 2; ++set)
       ST_HIP(bn_running_update(P.w(p + ".mlp.1.running_mean"), P.w(p + ".mlp.1.running_var"), y.ST + set * 6 * D, 2 * D,
                                kMomentum, c.st));
-    if (mlp_two_source()) {  // dW = GH^T [x | message]: columns < 256 from x, the rest from CAT[:, 256:]
+    {  // dW = GH^T [x | message]: columns < 256 from x, the rest from CAT[:, 256:]
       float* dW = P.gr(p + ".mlp.0.weight");
       float* db = P.gr(p + ".mlp.0.bias");
-      const bool fused = dW && db && tgemm_fuses_colsum(true, false);
       if (dW) {
         TGemm g{w.GH, X, dW, 2 * D, D, 2 * D, 0, 0, 0, 2 * D, 2 * D, R, 1, 1.f, 0.f, nullptr};
         g.B1 = y.CAT + D;
         g.ldb1 = 2 * D;
         g.N0 = D;
-        if (fused) g.colsumA = db;
+        g.colsumA = db;
         ST_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
+      } else if (db) {
+        ST_HIP(colsum(w.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st));
       }
-      if (db && !fused) ST_HIP(colsum(w.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st));
-    } else {
-      ST_HIP(linear_wgrad(c, w.GH, 2 * D, y.CAT, 2 * D, R, 2 * D, 2 * D, P.gr(p + ".mlp.0.weight"),
-                          P.gr(p + ".mlp.0.bias")));
     }
     ST_HIP(linear_dgrad(c, w.GH, 2 * D, R, 2 * D, P.w(p + ".mlp.0.weight"), 2 * D, w.GC, 2 * D));
     ST_HIP(add_rows256(GX, D, w.GC, 2 * D, GX2, D, R, c.st));  // residual + the mlp's x input

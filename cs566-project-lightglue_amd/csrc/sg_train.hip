@@ -441,16 +441,14 @@ __global__ void sk_col_final_kernel(const float* part, int B, int N1, int nch, f
 // the same expressions, so gC is bit-identical and the steps read C only.
 // The four waves' column sums are combined through ONE LDS row, wave by wave in order
 // (((w0 + w1) + w2) + w3, the order of the former four-row buffer): 34 KB of LDS instead of 59 KB,
-// four workgroups per CU instead of two.  PF (DEFER only): the wave's next row of C is loaded
-// while the current one is reduced.
+// four workgroups per CU instead of two.
 constexpr int SKF_Q = 33, SKF_R = 32;
 
-template <bool DEFER, bool PF>
+template <bool DEFER>
 __global__ __launch_bounds__(256) void sk_bwd_fused_kernel(const float* Cc, int M1, int N1, const float* u,
                                                            const float* v, const float* vp, const float* gv,
                                                            const float* base, float* gC, float norm, float lmu_last,
                                                            float lnu_last, float* gu_out, float* part) {
-  static_assert(DEFER || !PF, "prefetch only in the C-only step");
   __shared__ float v_s[64 * SKF_Q], vp_s[64 * SKF_Q], gv_s[64 * SKF_Q];
   __shared__ float red[64 * SKF_Q];
   const int b = blockIdx.y, w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -465,12 +463,6 @@ __global__ __launch_bounds__(256) void sk_bwd_fused_kernel(const float* Cc, int 
 #pragma unroll
   for (int q = 0; q < SKF_Q; ++q) cs[q] = 0.f;
   const int i0 = blockIdx.x * SKF_R, i1 = min(M1, i0 + SKF_R);
-  float xn[PF ? SKF_Q : 1];
-  if (PF && i0 + w < i1) {
-    const float* c = Cc + ((long long)b * M1 + i0 + w) * N1;
-#pragma unroll
-    for (int q = 0; q < (PF ? SKF_Q : 1); ++q) xn[q] = c[l + 64 * q];
-  }
   for (int i = i0 + w; i < i1; i += 4) {
     const long long row = (long long)b * M1 + i;
     const float* c = Cc + row * N1;
@@ -478,20 +470,10 @@ __global__ __launch_bounds__(256) void sk_bwd_fused_kernel(const float* Cc, int 
     const float ui = u[row], lmu = i < M1 - 1 ? norm : lmu_last;
     float x[SKF_Q], gx[SKF_Q];  // the gC row is read with C (its latency under the sums)
     float acc = 0.f;
-    if constexpr (PF) {
 #pragma unroll
-      for (int q = 0; q < SKF_Q; ++q) x[q] = xn[q];
-      if (i + 4 < i1) {
-        const float* cn = c + 4ll * N1;
-#pragma unroll
-        for (int q = 0; q < SKF_Q; ++q) xn[q] = cn[l + 64 * q];
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < SKF_Q; ++q) {  // unconditional loads (one base, immediate offsets): all in flight
-        x[q] = c[l + 64 * q];             // past the row end: the next row / the buffers' 64-float slack,
-        if (!DEFER) gx[q] = g[l + 64 * q];  // never used
-      }
+    for (int q = 0; q < SKF_Q; ++q) {  // unconditional loads (one base, immediate offsets): all in flight
+      x[q] = c[l + 64 * q];             // past the row end: the next row / the buffers' 64-float slack,
+      if (!DEFER) gx[q] = g[l + 64 * q];  // never used
     }
 #pragma unroll
     for (int q = 0; q < SKF_Q; ++q) {
@@ -969,27 +951,9 @@ hipError_t sk_train_forward(const float* cost, const float* alpha, int B, int M,
 
 size_t sk_train_row_slack_floats() { return 64 * SKF_Q; }
 
-#ifndef SG_SK_DEFER
-#define SG_SK_DEFER 1  // the Sinkhorn backward's gC terms in one pass after the steps (sk_bwd_accum_kernel)
-#endif
-static bool sk_defer(int N1, int iters) {
-  static const int v = [] {
-    const char* e = getenv("SG_SK_DEFER");
-    return e ? atoi(e) : SG_SK_DEFER;
-  }();
-  return v != 0 && skf_ok(N1) && iters >= 1 && iters <= SKA_TMAX;
-}
-
-#ifndef SG_SK_BWD_PF
-#define SG_SK_BWD_PF 0  // 1: the C-only backward step loads a wave's next row of C under the current one (slower)
-#endif
-static bool sk_bwd_pf() {
-  static const int v = [] {
-    const char* e = getenv("SG_SK_BWD_PF");
-    return e ? atoi(e) : SG_SK_BWD_PF;
-  }();
-  return v != 0;
-}
+// the Sinkhorn backward's gC terms in one pass after the steps (sk_bwd_accum_kernel) where the fused
+// step and the accumulation kernel take the shape
+static bool sk_defer(int N1, int iters) { return skf_ok(N1) && iters >= 1 && iters <= SKA_TMAX; }
 
 size_t sk_train_scratch_floats(int B, int M, int N, int iters) {
   // + every step's d/d u_t [T][B][M+1] and d/d v_t [T][B][N+1] for the deferred gC pass
@@ -1028,12 +992,8 @@ hipError_t sk_train_backward(const float* Cc, const float* U, const float* V, co
       const unsigned nwg = cdiv(M1, SKF_R);
       float* gut = GUall + (size_t)(t - 1) * B * M1;
       float* gvp = t > 1 ? GVall + (size_t)(t - 2) * B * N1 : gv2;  // d/d v_{t-1} (v_0 = 0: unused)
-      if (sk_bwd_pf())
-        hipLaunchKernelGGL((sk_bwd_fused_kernel<true, true>), dim3(nwg, B), dim3(256), 0, st, Cc, M1, N1, u, v, vp, gv,
-                           t == iters ? base : nullptr, gC, norm, lmu_last, lnu_last, gut, cpart);
-      else
-        hipLaunchKernelGGL((sk_bwd_fused_kernel<true, false>), dim3(nwg, B), dim3(256), 0, st, Cc, M1, N1, u, v, vp, gv,
-                           t == iters ? base : nullptr, gC, norm, lmu_last, lnu_last, gut, cpart);
+      hipLaunchKernelGGL((sk_bwd_fused_kernel<true>), dim3(nwg, B), dim3(256), 0, st, Cc, M1, N1, u, v, vp, gv,
+                         t == iters ? base : nullptr, gC, norm, lmu_last, lnu_last, gut, cpart);
       hipLaunchKernelGGL(sk_bwd_colsum_kernel, dim3(cdiv((long long)B * N1, 256)), dim3(256), 0, st, cpart, B, N1, (int)nwg,
                          gvp);
       gv = gvp;
@@ -1041,7 +1001,7 @@ hipError_t sk_train_backward(const float* Cc, const float* U, const float* V, co
     }
     if (skf_ok(N1)) {  // both halves of the step in one pass over C
       const unsigned nwg = cdiv(M1, SKF_R);
-      hipLaunchKernelGGL((sk_bwd_fused_kernel<false, false>), dim3(nwg, B), dim3(256), 0, st, Cc, M1, N1, u, v, vp, gv,
+      hipLaunchKernelGGL((sk_bwd_fused_kernel<false>), dim3(nwg, B), dim3(256), 0, st, Cc, M1, N1, u, v, vp, gv,
                          t == iters ? base : nullptr, gC, norm, lmu_last, lnu_last, gu, cpart);
       hipLaunchKernelGGL(sk_bwd_colsum_kernel, dim3(cdiv((long long)B * N1, 256)), dim3(256), 0, st, cpart, B, N1, (int)nwg,
                          gv2);

@@ -1,8 +1,16 @@
 // Host-visible launch wrappers of the training (autograd) kernels in train.hip (internal to
-// liblightglue_mi355x.so).  Every kernel computes in fp32: the products run on the f32-input
-// matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation, full fp32 range, so
-// gradients of any magnitude need no range scaling); reductions are deterministic (fixed-order
-// partial sums) except the attention backward's dQ, which is summed with float atomics.
+// liblightglue_mi355x.so).  Every kernel takes and returns fp32 and accumulates in fp32, with the
+// full fp32 range, so gradients of any magnitude need no range scaling.  The route of a product
+// follows from its shape and alignment alone:
+//   * bf16x6 (common.h: each fp32 operand split into three bf16 pieces, six v_mfma_f32_32x32x16_bf16
+//     per block; error per product ~2^-24 like an f32 fma chain, at the bf16 rate): tgemm's
+//     k-contiguous products (ta = 0) with K % 16 == 0 and 16-byte-aligned operands, every weight
+//     gradient (ta = 1, tb = 0), and the attention's S, P V, dP, dV and dK;
+//   * f32 MFMA (v_mfma_f32_32x32x2_f32 / 16x16x4_f32: exact fp32 products): tgemm's remaining shapes
+//     (K % 16 != 0, unaligned operands, ta && tb) and the attention backward's dQ, whose dS
+//     operand is already in LDS as fp32.
+// Reductions are deterministic (fixed-order partial sums) except the attention backward's dQ, which
+// is summed with float atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -26,14 +34,14 @@ struct TGemm {
   float alpha, beta;
   const float* bias;
   // ta = 1 only: also out[b][m] = sum_k A[b][k][m] (the column sums of the k-major A: a linear
-  // layer's bias gradient beside its weight gradient, from the same read of dY) -- honoured when
-  // tgemm_fuses_colsum(ta, tb) says so, otherwise ignored
+  // layer's bias gradient beside its weight gradient, from the same read of dY) -- honoured for
+  // ta && !tb, otherwise ignored
   float* colsumA = nullptr;
   // R (ldr): the beta term reads R instead of C, C = alpha (op(A) op(B) + bias) + beta R -- a
   // residual added on the way out (batch 1), without first copying it into C
   const float* R = nullptr;
   long long ldr = 0;
-  // Two-source operands (batch 1; used only where tgemm_two_source() says the routes are on):
+  // Two-source operands (batch 1):
   //   A1 (ta = 0, tb = 1: the bf16x6 A B^T route): op(A)(m, k) = k < K0 ? A[m lda + k] : A1[m lda1 + k - K0]
   //   B1 (ta = 1, tb = 0: the vectorised bf16x6 weight-gradient route; N0 % 128 == 0):
   //      op(B)(k, n) = n < N0 ? B[k ldb + n] : B1[k ldb1 + n - N0]
@@ -46,12 +54,8 @@ struct TGemm {
   long long ldb1 = 0;
   int N0 = 0;
 };
-bool tgemm_two_source(int x6);  // both two-source routes are on for tgemm(..., x6)
 size_t tgemm_ws_floats(int M, int N, int K, int batch);
-bool tgemm_fuses_colsum(bool ta, bool tb);
-// x6: allow the bf16x6 route for k-contiguous products (train.hip tgemm_x6); false = f32 MFMA only
-// x6: 0 f32 MFMA only; 1 the bf16x6 routes the build enables (LG_TG_X6*); 2 also A B^T forms (tb)
-hipError_t tgemm(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st, int x6 = 1);
+hipError_t tgemm(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st);
 
 // Attention on row-major fp32 tensors (row stride ld*, head h at columns [64h, 64h+64)); item
 // (b, h): queries rows [b*Nq, (b+1)*Nq) of Q, keys / values rows [b*Nk, (b+1)*Nk) of K / V.

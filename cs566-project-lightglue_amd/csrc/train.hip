@@ -2,11 +2,12 @@
 // gluefactory/models/matchers/lightglue.py:159-315 differentiated by torch autograd in
 // gluefactory/train.py:450) and the activation-saving training forward it needs.
 //
-// Arithmetic: fp32 throughout.  The matrix products use v_mfma_f32_32x32x2_f32 (exact fp32
-// products, fp32 accumulation in k order; MI355X_MICROARCH.md / cdna_hip_programming.md
-// "FP32-input MFMA"), so a gradient of any magnitude is represented as fp32 represents it: no
-// range scaling, no split operands.  Lane map (common.h row32): A[l&31][l>>5], B[l>>5][l&31],
-// accumulator register r of lane l = C[row32(r, l>>5)][l&31].
+// Arithmetic: fp32 in, fp32 accumulation, fp32 out, so a gradient of any magnitude is represented
+// as fp32 represents it: no range scaling.  Which products run as bf16x6 (three bf16 pieces per
+// operand, common.h) and which on the f32-input MFMA (v_mfma_f32_32x32x2_f32, exact fp32 products)
+// follows from shape and alignment alone: train.h lists the routes.  Lane map of the f32 MFMA
+// (common.h row32): A[l&31][l>>5], B[l>>5][l&31], accumulator register r of lane l =
+// C[row32(r, l>>5)][l&31].
 #include <algorithm>
 #include <cmath>
 
@@ -525,27 +526,14 @@ int tgemm_split(int M, int N, int K, int batch, int& kchunk) {
 }
 
 // ============================================================================ attention
-// Forward: a workgroup = 4 waves x 32 queries of one (pair, head); the query sits on the MFMA
+// Forward: a workgroup = W waves x 32 queries of one (pair, head); the query sits on the MFMA
 // lane (S^T = K Q^T), so the online softmax runs in-register per lane (the two lane halves hold
 // different keys of the same query: one v_permlane32_swap per max) and P^T is directly the B
-// operand of O^T = V^T P^T (the permuted key order row32 on both operands).  K / V tiles of 64
-// keys double-buffered in LDS (pitches 66 / 72: conflict-free for the two read patterns).
-constexpr int TA_KP = 66, TA_VP = 72;
-
-__device__ __forceinline__ void load_head_row_frag(const float* row, int h, float (&f)[32]) {
-  // f[s] = row[2s + h], s < 32, from 16 float4 loads of the 64-float head row
-#pragma unroll
-  for (int s4 = 0; s4 < 16; ++s4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * s4);
-    f[2 * s4] = h ? v[1] : v[0];
-    f[2 * s4 + 1] = h ? v[3] : v[2];
-  }
-}
-
-// The same forward on bf16 matrix cores (bf16x6, common.h): S^T = K Q^T and O^T = V^T P^T as six
+// operand of O^T = V^T P^T (the permuted key order row32 on both operands).
+// Both products run on bf16 matrix cores (bf16x6, common.h): S^T = K Q^T and O^T = V^T P^T as six
 // v_mfma_f32_32x32x16_bf16 per 32 x 32 x 16 block, every operand split into three bf16 pieces
 // (the fp32-accurate product at the bf16 rate).  The query's pieces sit in registers (scaled by
-// scale log2 e before the split, as above); a 64-key tile of K is staged [key][dim] and of V
+// scale log2 e before the split); a 64-key tile of K is staged [key][dim] and of V
 // transposed [dim][key] as three bf16 planes each, 16-byte chunks XOR-swizzled by row.  The V^T
 // chunks hold the keys in the accumulator's row32 order, so P^T goes from the S^T accumulators
 // straight into the B operand (split per value).  One LDS buffer: the next tile waits in
@@ -722,128 +710,6 @@ __global__ __launch_bounds__(64 * W, 8 / W) void tattn_fwd_x6_kernel(TAttn a) {
   if (h == 0) a.lse[(long long)item * a.Nq + qrow] = m + log2f(lsum);
 }
 
-__global__ __launch_bounds__(256) void tattn_fwd_kernel(TAttn a) {
-  __shared__ __attribute__((aligned(16))) float Ks[2][64 * TA_KP];
-  __shared__ __attribute__((aligned(16))) float Vs[2][64 * TA_VP];
-  const int t = threadIdx.x, w = t >> 6, l = t & 63, h = l >> 5, l32 = l & 31;
-  const int item = blockIdx.y, b = item / a.H, hd = item - b * a.H;
-  const float* Q = a.Q + (long long)b * a.Nq * a.ldq + hd * 64;
-  const float* K = a.K + (long long)b * a.Nk * a.ldk + hd * 64;
-  const float* V = a.V + (long long)b * a.Nk * a.ldv + hd * 64;
-  const int qrow = blockIdx.x * 128 + w * 32 + l32;
-  const bool qv = qrow < a.Nq;
-  const float c = a.scale * kLog2e;
-  float qf[32];
-  if (qv) {
-    load_head_row_frag(Q + (long long)qrow * a.ldq, h, qf);
-#pragma unroll
-    for (int s = 0; s < 32; ++s) qf[s] *= c;
-  } else {
-#pragma unroll
-    for (int s = 0; s < 32; ++s) qf[s] = 0.f;
-  }
-  // K / V tile staging: 64 rows x 64 floats; thread t -> rows (t>>4) + 16q, columns 4(t&15)..+3
-  const int sr = t >> 4, sc = (t & 15) * 4;
-  f32x4 rk[4], rv[4];
-  auto load_kv = [&](int kt) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int key = kt * 64 + sr + 16 * q;
-      if (key < a.Nk) {
-        rk[q] = *reinterpret_cast<const f32x4*>(K + (long long)key * a.ldk + sc);
-        rv[q] = *reinterpret_cast<const f32x4*>(V + (long long)key * a.ldv + sc);
-      } else {
-        rk[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        rv[q] = rk[q];
-      }
-    }
-  };
-  auto store_kv = [&](int st) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float* kp = Ks[st] + (sr + 16 * q) * TA_KP + sc;
-      *reinterpret_cast<f32x2*>(kp) = f32x2{rk[q][0], rk[q][1]};
-      *reinterpret_cast<f32x2*>(kp + 2) = f32x2{rk[q][2], rk[q][3]};
-      *reinterpret_cast<f32x4*>(Vs[st] + (sr + 16 * q) * TA_VP + sc) = rv[q];
-    }
-  };
-  const int nkt = (a.Nk + 63) / 64;
-  float m = -INFINITY, lsum = 0.f;
-  f32x16 ot[2] = {zero16(), zero16()};
-  load_kv(0);
-  store_kv(0);
-  __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nkt) load_kv(kt + 1);
-    const float* ks = Ks[cur];
-    f32x16 st[2] = {zero16(), zero16()};
-#pragma unroll
-    for (int s = 0; s < 32; ++s) {
-      const float k0 = ks[l32 * TA_KP + 2 * s + h];
-      const float k1 = ks[(32 + l32) * TA_KP + 2 * s + h];
-      st[0] = mfma32(k0, qf[s], st[0]);
-      st[1] = mfma32(k1, qf[s], st[1]);
-    }
-    if (kt * 64 + 64 > a.Nk) {
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt * 64 + 32 * tt + row32(r, h) >= a.Nk) st[tt][r] = -INFINITY;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[tt][r]);
-    mx = max_xor32(mx);
-    const float mn = fmaxf(m, mx);
-    const float base = mn == -INFINITY ? 0.f : mn;
-    const float f = exp2f(m - base);
-    lsum *= f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      ot[0][r] *= f;
-      ot[1][r] *= f;
-    }
-    m = mn;
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = exp2f(st[tt][r] - base);
-        st[tt][r] = pv;
-        lsum += pv;
-      }
-    const float* vs = Vs[cur];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float* vr = vs + (32 * tt + row32(r, h)) * TA_VP + l32;
-        ot[0] = mfma32(vr[0], st[tt][r], ot[0]);
-        ot[1] = mfma32(vr[32], st[tt][r], ot[1]);
-      }
-    if (kt + 1 < nkt) store_kv(cur ^ 1);
-    __syncthreads();
-  }
-  lsum = sum_xor32(lsum);
-  if (!qv) return;
-  const float inv = 1.f / lsum;
-  float* O = a.O + ((long long)b * a.Nq + qrow) * a.ldo + hd * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = ot[dt][4 * g4 + e] * inv;
-      *reinterpret_cast<f32x4*>(O + 32 * dt + 8 * g4 + 4 * h) = v;
-    }
-  if (h == 0) a.lse[(long long)item * a.Nq + qrow] = m + log2f(lsum);
-}
-
 // Backward: a workgroup = 8 waves x 32 keys (256 keys) of one (pair, head); the key sits on the
 // lane, so S and dP come out with their columns = keys and are directly the B operands of
 // dV^T += dO^T P and dK^T += Q^T dS (permuted query order row32 on both operands).  Row constants
@@ -854,161 +720,14 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(TAttn a) {
 // segments per instruction).  Against 4 waves x 128 keys with 32 x 32 dQ quarters: a quarter of
 // the atomic bytes, and two waves per SIMD.
 constexpr int TB_W = 8, TB_KEYS = 32 * TB_W;
-constexpr int TB_QP = 66, TB_KP = 80, TB_DP = TB_KEYS + 4;
+constexpr int TB_DP = TB_KEYS + 4;
 
-__global__ __launch_bounds__(64 * TB_W) void tattn_bwd_kernel(TAttn a) {
-  // one Q / dO tile buffer: the next tile waits in registers and lands after the barrier that
-  // ends this tile's reads of it
-  __shared__ __attribute__((aligned(16))) float Qs[32 * TB_QP];
-  __shared__ __attribute__((aligned(16))) float dOs[32 * TB_QP];
-  __shared__ __attribute__((aligned(16))) float Kall[TB_KEYS * TB_KP];
-  __shared__ __attribute__((aligned(16))) float dSs[32 * TB_DP];
-  __shared__ float lse_s[32], del_s[32];
-  const int t = threadIdx.x, w = t >> 6, l = t & 63, h = l >> 5, l32 = l & 31;
-  const int item = blockIdx.y, b = item / a.H, hd = item - b * a.H;
-  const float* Q = a.Q + (long long)b * a.Nq * a.ldq + hd * 64;
-  const float* dO = a.dO + (long long)b * a.Nq * a.ldo + hd * 64;
-  const float* K = a.K + (long long)b * a.Nk * a.ldk + hd * 64;
-  const float* V = a.V + (long long)b * a.Nk * a.ldv + hd * 64;
-  const float* lse = a.lse + (long long)item * a.Nq;
-  const float* del = a.delta + (long long)item * a.Nq;
-  const int kb0 = blockIdx.x * TB_KEYS;
-  const int key = kb0 + w * 32 + l32;
-  const bool kv = key < a.Nk;
-  const float c = a.scale * kLog2e;
-  float kf[32], vf[32];
-  if (kv) {
-    load_head_row_frag(K + (long long)key * a.ldk, h, kf);
-    load_head_row_frag(V + (long long)key * a.ldv, h, vf);
-#pragma unroll
-    for (int s = 0; s < 32; ++s) kf[s] *= c;
-  } else {
-#pragma unroll
-    for (int s = 0; s < 32; ++s) kf[s] = vf[s] = 0.f;
-  }
-  // the workgroup's 256 keys (unscaled) for dQ: thread t -> rows (t>>4) + 32q, q < 8
-  {
-    const int sr = t >> 4, sc = (t & 15) * 4;
-#pragma unroll
-    for (int q = 0; q < TB_KEYS / 32; ++q) {
-      const int k = kb0 + sr + 32 * q;
-      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (k < a.Nk) v = *reinterpret_cast<const f32x4*>(K + (long long)k * a.ldk + sc);
-      *reinterpret_cast<f32x4*>(Kall + (sr + 32 * q) * TB_KP + sc) = v;
-    }
-  }
-  // query tiles: 32 rows x 64 floats of Q and dO; thread t -> row t>>4, columns 4(t&15)..+3
-  const int sr = t >> 4, sc = (t & 15) * 4;
-  f32x4 rq, rd;
-  float rl = 0.f, rdl = 0.f;
-  auto load_q = [&](int qt) {
-    const int qi = qt * 32 + sr;
-    if (qi < a.Nq) {
-      rq = *reinterpret_cast<const f32x4*>(Q + (long long)qi * a.ldq + sc);
-      rd = *reinterpret_cast<const f32x4*>(dO + (long long)qi * a.ldo + sc);
-    } else {
-      rq = f32x4{0.f, 0.f, 0.f, 0.f};
-      rd = rq;
-    }
-    if (t < 32) {
-      const int qj = qt * 32 + t;
-      rl = qj < a.Nq ? lse[qj] : INFINITY;  // padded queries: p = exp2(-inf) = 0
-      rdl = qj < a.Nq ? del[qj] : 0.f;
-    }
-  };
-  auto store_q = [&]() {
-    float* qp = Qs + sr * TB_QP + sc;
-    float* dp = dOs + sr * TB_QP + sc;
-    *reinterpret_cast<f32x2*>(qp) = f32x2{rq[0], rq[1]};
-    *reinterpret_cast<f32x2*>(qp + 2) = f32x2{rq[2], rq[3]};
-    *reinterpret_cast<f32x2*>(dp) = f32x2{rd[0], rd[1]};
-    *reinterpret_cast<f32x2*>(dp + 2) = f32x2{rd[2], rd[3]};
-    if (t < 32) {
-      lse_s[t] = rl;
-      del_s[t] = rdl;
-    }
-  };
-  f32x16 dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};
-  const int nqt = (a.Nq + 31) / 32;
-  const int qh = w & 1, dq = w >> 1;  // this wave's dQ tile: queries 16 qh .., dims 16 dq ..
-  const int l16 = l & 15, lk = l >> 4;
-  float* dQ = a.dQ + (long long)b * a.Nq * a.ldq + hd * 64 + 16 * dq + l16;
-  load_q(0);
-  store_q();
-  __syncthreads();
-  for (int qt = 0; qt < nqt; ++qt) {
-    if (qt + 1 < nqt) load_q(qt + 1);
-    f32x16 sacc, pacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sacc[r] = -lse_s[row32(r, h)];
-      pacc[r] = -del_s[row32(r, h)];
-    }
-#pragma unroll
-    for (int s = 0; s < 32; ++s) {
-      sacc = mfma32(Qs[l32 * TB_QP + 2 * s + h], kf[s], sacc);
-      pacc = mfma32(dOs[l32 * TB_QP + 2 * s + h], vf[s], pacc);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float p = kv ? exp2f(sacc[r]) : 0.f;
-      sacc[r] = p;
-      pacc[r] *= p;  // dS (w.r.t. the scaled scores)
-    }
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qr = row32(r, h) * TB_QP + 32 * dt + l32;
-        dvt[dt] = mfma32(dOs[qr], sacc[r], dvt[dt]);
-        dkt[dt] = mfma32(Qs[qr], pacc[r], dkt[dt]);
-      }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dSs[row32(r, h) * TB_DP + w * 32 + l32] = pacc[r];
-    __syncthreads();
-    f32x4 qacc = {0.f, 0.f, 0.f, 0.f};
-    const float* ds_row = dSs + (16 * qh + l16) * TB_DP + lk;
-    const float* k_col = Kall + lk * TB_KP + 16 * dq + l16;
-#pragma unroll 16
-    for (int s = 0; s < TB_KEYS / 4; ++s)
-      qacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ds_row[4 * s], k_col[4 * s * TB_KP], qacc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qi = qt * 32 + 16 * qh + 4 * lk + r;
-      if (qi < a.Nq) atomicAdd(dQ + (long long)qi * a.ldq, qacc[r] * a.scale);
-    }
-    if (qt + 1 < nqt) store_q();  // every wave is past this tile's reads of Qs / dOs (barrier above)
-    __syncthreads();
-  }
-  if (!kv) return;
-  float* dK = a.dK + ((long long)b * a.Nk + key) * a.ldk + hd * 64;
-  float* dV = a.dV + ((long long)b * a.Nk + key) * a.ldv + hd * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int d0 = 32 * dt + 8 * g4 + 4 * h;
-      f32x4 vk, vv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        vk[e] = dkt[dt][4 * g4 + e] * a.scale;
-        vv[e] = dvt[dt][4 * g4 + e];
-      }
-      if (a.accum_kv) {
-        vk += *reinterpret_cast<const f32x4*>(dK + d0);
-        vv += *reinterpret_cast<const f32x4*>(dV + d0);
-      }
-      *reinterpret_cast<f32x4*>(dK + d0) = vk;
-      *reinterpret_cast<f32x4*>(dV + d0) = vv;
-    }
-}
-
-// The same backward with S, dP, dV^T and dK^T on bf16 matrix cores (bf16x6, common.h): the key's
+// S, dP, dV^T and dK^T run on bf16 matrix cores (bf16x6, common.h): the key's
 // K (scaled by scale log2 e) and V sit in registers as three bf16 pieces; a query tile is staged
 // [query][dim] (A operand of S = Q K^T and dP = dO V^T) and [dim][query] (A operand of dV^T and
 // dK^T, the queries of each 16-byte chunk in the row32 order the S / dP accumulators hold them
 // in), three bf16 planes each.  P and dS go from the accumulators into the B operands split per
-// value.  dQ stays on v_mfma_f32_16x16x4_f32 over fp32 dS / K exactly as tattn_bwd_kernel.
+// value.  dQ stays on v_mfma_f32_16x16x4_f32 over fp32 dS / K.
 __device__ __forceinline__ int x6_swt(int row, int chunk) { return (chunk ^ ((row >> 2) & 3)) * 8; }
 
 #ifndef LG_TB_PROBE
@@ -1596,11 +1315,8 @@ __global__ __launch_bounds__(256) void sim_lse_col_part4_kernel(const float* sim
 // workgroup's rows is the partial sim_lse_col_final_kernel merges.  The next row's values are
 // loaded while the current one is reduced.
 constexpr int SLF_ROWS = 32;
-#ifndef LG_SLF_RP
-#define LG_SLF_RP 1
-#endif
-// RP rows per step, the next RP prefetched (measured per launch at N = 2048: RP 1 172 us, 2 193 us,
-// 4 199 us; the two-pass kernels 137 + 123 us, profiles/r05/lse_fused/)
+// RP rows per step, the next RP prefetched; only RP = 1 is instantiated (measured per launch at
+// N = 2048: RP 1 172 us, 2 193 us, 4 199 us; the two-pass kernels 137 + 123 us, profiles/r05/lse_fused/)
 template <int QN, int RP>
 __global__ __launch_bounds__(256) void sim_lse_fused_kernel(const float* sim, int M, int N, float* lser, float2* part) {
   __shared__ float2 rst[SLF_ROWS][4];
@@ -2106,9 +1822,6 @@ __global__ __launch_bounds__(256) void la_forward_rows_kernel(const float* sim, 
 //   * per column, the maximum over the workgroup's rows (first maximum; row M = the dustbin row
 //     joins it), merged over the workgroups by la_nll_cols_kernel.
 constexpr int LN_R = 32;
-#ifndef LG_NLL_PF
-#define LG_NLL_PF 1
-#endif
 int ln_blocks(int M) { return (M + 1 + LN_R - 1) / LN_R; }
 
 __device__ __forceinline__ void argmax_merge(float& v, int& i, float v2, int i2) {
@@ -2120,7 +1833,8 @@ __device__ __forceinline__ void argmax_merge(float& v, int& i, float v2, int i2)
 
 // KC: columns per thread / 256 (N <= 256 KC; the column tables in LDS sized to it, so more
 // workgroups fit a CU).  PF: the next row's similarity and ground truth are loaded while the
-// current row is reduced (one row's memory latency in flight behind another's arithmetic).
+// current row is reduced (one row's memory latency in flight behind another's arithmetic); only
+// PF = true is instantiated.
 template <int KC, bool PF>
 __global__ __launch_bounds__(256) void la_nll_rows_kernel(const float* sim, const float* lser, const float* lsec,
                                                           const float* z0, const float* z1, int B, int M, int N,
@@ -2374,44 +2088,13 @@ size_t tgemm_ws_floats(int M, int N, int K, int batch) {
   return ks > 1 ? (size_t)ks * M * (N + 1) * batch : 0;  // + the column-sum partials
 }
 
-#ifndef LG_TG_X6_FWD
-// 1: LightGlue's forward products (ta = 0, tb = 1) too (SuperGlue's pass mode 0 / 2 and ignore
-// this).  Round 5: on since the N = 512 gradient golden and the refined bar: worst
-// err / bar 0.86 at N = 512, 0.62 at N = 64 (it was 1.16 under the round-4 heads-on-f32 mix);
-// LightGlue step 248.8 -> 235.0 ms (profiles/r05/train_s2/bench_train_fwd*.json)
-#define LG_TG_X6_FWD 1
-#endif
-#ifndef LG_TG_X6_WGRAD
-#define LG_TG_X6_WGRAD 1  // weight gradients (ta = 1, tb = 0) on the bf16x6 kernel tgemm_x6t_kernel
-#endif
-#ifndef LG_TG_X6
-#define LG_TG_X6 1  // route k-contiguous products to the bf16x6 GEMM (LG_TG_X6=0 at run time: f32 MFMA only)
-#endif
-static bool tg_x6_enabled() {
-  static const int v = [] {
-    const char* e = getenv("LG_TG_X6");
-    return e ? atoi(e) : LG_TG_X6;
-  }();
-  return v != 0;
-}
-
 // The products whose operands both run along k in memory -- a linear layer's forward
 // (ta = 0, tb = 1), and its input gradient (ta = 0, tb = 0) once the weight is transposed into
 // `ws` -- go to gemm.hip's bf16x6 kernel: both fp32 operands split into three bf16 pieces, six
 // v_mfma_f32_32x32x16_bf16 per 32 x 32 x 16 block (the fp32-accurate product of common.h at
 // 2.5 PF/s bf16 instead of the 157 TF/s f32 MFMA); error per product ~2^-24 like an f32 fma chain.
-static bool tg_x6_fwd() {  // env LG_TG_X6_FWD overrides the build's default (A/B runs)
-  static const int v = [] {
-    const char* e = getenv("LG_TG_X6_FWD");
-    return e ? atoi(e) : LG_TG_X6_FWD;
-  }();
-  return v != 0;
-}
-
-static bool tgemm_x6(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st, int mode,
-                     hipError_t& err) {
-  if (!tg_x6_enabled() || ta || g.K < 16 || g.K % 16 || (g.beta != 0.f && g.beta != 1.f)) return false;
-  if (tb && !tg_x6_fwd() && mode < 2) return false;
+static bool tgemm_x6(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st, hipError_t& err) {
+  if (ta || g.K < 16 || g.K % 16 || (g.beta != 0.f && g.beta != 1.f)) return false;
   auto al = [](const void* ptr, long long ld, long long sb) {
     return ((uintptr_t)ptr % 16 == 0) && ld % 4 == 0 && sb % 4 == 0;
   };
@@ -2455,36 +2138,15 @@ static bool tgemm_x6(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floa
   return true;
 }
 
-#ifndef LG_X6T_VEC
-// 1: weight gradients on tgemm_x6tv_kernel (16-byte loads, transposed LDS reads, XCD-grouped k-chunks);
-// round 5: 8-13 % faster per launch than tgemm_x6t_kernel, LightGlue step -4.6 ms (profiles/r05/x6t_vec*)
-#define LG_X6T_VEC 1
-#endif
-static bool tg_x6t_vec() {
-  static const int v = [] {
-    const char* e = getenv("LG_X6T_VEC");
-    return e ? atoi(e) : LG_X6T_VEC;
-  }();
-  return v != 0;
-}
-
-bool tgemm_fuses_colsum(bool ta, bool tb) { return ta && !tb && tg_x6_enabled() && LG_TG_X6_WGRAD; }
-
-bool tgemm_two_source(int x6) {
-  // tgemm_x6's own conditions for an A B^T product at this mode, and the vectorised weight gradient
-  return x6 && tg_x6_enabled() && (x6 >= 2 || tg_x6_fwd()) && LG_TG_X6_WGRAD && tg_x6t_vec();
-}
-
-hipError_t tgemm(const TGemm& g_in, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st, int x6) {
+hipError_t tgemm(const TGemm& g_in, bool ta, bool tb, float* ws, size_t ws_floats, hipStream_t st) {
   TGemm g = g_in;
-  if (!(x6 && tgemm_fuses_colsum(ta, tb))) g.colsumA = nullptr;  // only the bf16x6 weight-gradient kernel sums
+  if (!(ta && !tb)) g.colsumA = nullptr;  // only the bf16x6 weight-gradient kernels sum
   if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return hipSuccess;
   if (g.colsumA && g.K <= 0) return hipMemsetAsync(g.colsumA, 0, sizeof(float) * g.M * g.batch, st);
   hipError_t xe = hipSuccess;
-  if (x6 && tgemm_x6(g, ta, tb, ws, ws_floats, st, x6, xe)) return xe;
+  if (tgemm_x6(g, ta, tb, ws, ws_floats, st, xe)) return xe;
   if (g.A1) return hipErrorInvalidValue;  // the two-source A exists on the bf16x6 route only
-  if (g.B1 && (g.batch != 1 || g.N0 % X6_BN || !ta || tb || !x6 || !tg_x6_enabled() || !LG_TG_X6_WGRAD))
-    return hipErrorInvalidValue;
+  if (g.B1 && (g.batch != 1 || g.N0 % X6_BN || !ta || tb)) return hipErrorInvalidValue;
   if (g.R) {  // the f32 kernels read the beta term from C: put the residual there first
     if (g.batch != 1) return hipErrorInvalidValue;
     const hipError_t e = hipMemcpy2DAsync(g.C, g.ldc * sizeof(float), g.R, g.ldr * sizeof(float), g.N * sizeof(float), g.M,
@@ -2510,8 +2172,8 @@ hipError_t tgemm(const TGemm& g_in, bool ta, bool tb, float* ws, size_t ws_float
   p.vecA = aligned(g.A, g.lda, g.sA);
   p.vecB = aligned(g.B, g.ldb, g.sB);
   const dim3 grid(cdiv(g.M, TG_BM), cdiv(g.N, TG_BN), g.batch * p.ksplit);
-  if (x6 && ta && !tb && tg_x6_enabled() && LG_TG_X6_WGRAD) {  // weight gradients on bf16x6
-    const bool vec = tg_x6t_vec() && g.M % 4 == 0 && g.N % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
+  if (ta && !tb) {  // weight gradients on bf16x6: the vectorised kernel, tgemm_x6t_kernel for unaligned operands
+    const bool vec = g.M % 4 == 0 && g.N % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
                      g.sA % 4 == 0 && g.sB % 4 == 0 && (uintptr_t)g.A % 16 == 0 && (uintptr_t)g.B % 16 == 0;
     if (g.B1 && !(vec && (uintptr_t)g.B1 % 16 == 0 && g.ldb1 % 4 == 0)) return hipErrorInvalidValue;
     if (vec) hipLaunchKernelGGL(tgemm_x6tv_kernel, grid, dim3(256), 0, st, p);
@@ -2525,7 +2187,6 @@ hipError_t tgemm(const TGemm& g_in, bool ta, bool tb, float* ws, size_t ws_float
   }
   if (!ta && !tb) hipLaunchKernelGGL((tgemm_kernel<false, false>), grid, dim3(256), 0, st, p);
   else if (!ta && tb) hipLaunchKernelGGL((tgemm_kernel<false, true>), grid, dim3(256), 0, st, p);
-  else if (ta && !tb) hipLaunchKernelGGL((tgemm_kernel<true, false>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((tgemm_kernel<true, true>), grid, dim3(256), 0, st, p);
   if (p.ksplit > 1)
     hipLaunchKernelGGL(tgemm_reduce_kernel, dim3(cdiv((long long)g.M * g.N * g.batch, 256)), dim3(256), 0, st, p,
@@ -2533,51 +2194,16 @@ hipError_t tgemm(const TGemm& g_in, bool ta, bool tb, float* ws, size_t ws_float
   return hipGetLastError();
 }
 
-#ifndef LG_TA_W
-#define LG_TA_W 8  // waves per workgroup of tattn_fwd_x6_kernel (4 or 8)
-#endif
-#ifndef LG_TA_X6
-#define LG_TA_X6 1  // the training attention forward on bf16x6 (tattn_fwd_x6_kernel); 0: f32 MFMA
-#endif
-static bool ta_x6_enabled() {
-  static const int v = [] {
-    const char* e = getenv("LG_TA_X6");
-    return e ? atoi(e) : LG_TA_X6;
-  }();
-  return v != 0;
-}
-
 hipError_t tattn_forward(const TAttn& a, hipStream_t st) {
   if (a.B * a.H == 0 || a.Nq == 0) return hipSuccess;
-  if (ta_x6_enabled() && a.Nk > 0) {
-    if (LG_TA_W == 8)
-      hipLaunchKernelGGL(tattn_fwd_x6_kernel<8>, dim3(cdiv(a.Nq, 256), a.B * a.H), dim3(512), 0, st, a);
-    else
-      hipLaunchKernelGGL(tattn_fwd_x6_kernel<4>, dim3(cdiv(a.Nq, 128), a.B * a.H), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(tattn_fwd_kernel, dim3(cdiv(a.Nq, 128), a.B * a.H), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(tattn_fwd_x6_kernel<8>, dim3(cdiv(a.Nq, 256), a.B * a.H), dim3(512), 0, st, a);
   return hipGetLastError();
 }
 
-#ifndef LG_TB_X6
-#define LG_TB_X6 1  // the training attention backward on bf16x6 (tattn_bwd_x6_kernel); 0: f32 MFMA
-#endif
-static bool tb_x6_enabled() {
-  static const int v = [] {
-    const char* e = getenv("LG_TB_X6");
-    return e ? atoi(e) : LG_TB_X6;
-  }();
-  return v != 0;
-}
-
+// Nq == 0 (no query tiles): dK / dV are written as zeros, or left as they are under accum_kv
 hipError_t tattn_backward(const TAttn& a, hipStream_t st) {
   if (a.B * a.H == 0 || a.Nk == 0) return hipSuccess;
-  if (tb_x6_enabled() && a.Nq > 0) {
-    hipLaunchKernelGGL(tattn_bwd_x6_kernel, dim3(cdiv(a.Nk, TB_KEYS), a.B * a.H), dim3(64 * TB_W), 0, st, a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(tattn_bwd_kernel, dim3(cdiv(a.Nk, TB_KEYS), a.B * a.H), dim3(64 * TB_W), 0, st, a);
+  hipLaunchKernelGGL(tattn_bwd_x6_kernel, dim3(cdiv(a.Nk, TB_KEYS), a.B * a.H), dim3(64 * TB_W), 0, st, a);
   return hipGetLastError();
 }
 
@@ -2732,29 +2358,13 @@ size_t sim_lse_part_floats(int B, int M, int N) {
 
 hipError_t sim_lse(const float* sim, int B, int M, int N, float* lser, float* lsec, float* part, hipStream_t st) {
   if (B * M == 0 || N == 0) return hipSuccess;
-  static const bool fused = [] {
-    const char* e = getenv("LG_SIM_LSE_FUSED");
-    return e ? atoi(e) != 0 : true;
-  }();
-  if (fused && N % 4 == 0 && N <= 4096 && (reinterpret_cast<uintptr_t>(sim) & 15) == 0) {
+  if (N % 4 == 0 && N <= 4096 && (reinterpret_cast<uintptr_t>(sim) & 15) == 0) {
     const int nch = (int)cdiv(M, SLF_ROWS);
     float2* p2 = reinterpret_cast<float2*>(part);
-    static const int rp = [] {
-      const char* e = getenv("LG_SLF_RP");
-      const int v = e ? atoi(e) : LG_SLF_RP;
-      return v == 2 || v == 4 ? v : 1;
-    }();
-#define LG_SLF(QN, RP) hipLaunchKernelGGL((sim_lse_fused_kernel<QN, RP>), dim3(nch, B), dim3(256), 0, st, sim, M, N, lser, p2)
-#define LG_SLF_Q(QN)            \
-  do {                          \
-    if (rp == 1) LG_SLF(QN, 1); \
-    else if (rp == 4) LG_SLF(QN, 4); \
-    else LG_SLF(QN, 2);         \
-  } while (0)
-    if (N <= 1024) LG_SLF_Q(1);
-    else if (N <= 2048) LG_SLF_Q(2);
-    else LG_SLF_Q(4);
-#undef LG_SLF_Q
+#define LG_SLF(QN) hipLaunchKernelGGL((sim_lse_fused_kernel<QN, 1>), dim3(nch, B), dim3(256), 0, st, sim, M, N, lser, p2)
+    if (N <= 1024) LG_SLF(1);
+    else if (N <= 2048) LG_SLF(2);
+    else LG_SLF(4);
 #undef LG_SLF
     hipLaunchKernelGGL(sim_lse_col_final_kernel, dim3(cdiv((long long)B * N, 256)), dim3(256), 0, st, p2, nch, B, N, lsec);
     return hipGetLastError();
@@ -2866,23 +2476,12 @@ hipError_t la_nll(const float* sim, const float* lser, const float* lsec, const 
   double* dp = reinterpret_cast<double*>(part);
   float* cval = part + 4 * (size_t)B * nblk;
   int* cidx = reinterpret_cast<int*>(cval + (size_t)B * nblk * N);
-  static const bool pf = [] {
-    const char* e = getenv("LG_NLL_PF");
-    return e ? atoi(e) != 0 : LG_NLL_PF != 0;
-  }();
-#define LG_NLL_ROWS(KC, PF)                                                                                          \
-  hipLaunchKernelGGL((la_nll_rows_kernel<KC, PF>), dim3(nblk, B), dim3(256), 0, st, sim, lser, lsec, z0, z1, B, M, N, gta, \
+#define LG_NLL_ROWS(KC)                                                                                                \
+  hipLaunchKernelGGL((la_nll_rows_kernel<KC, true>), dim3(nblk, B), dim3(256), 0, st, sim, lser, lsec, z0, z1, B, M, N, gta, \
                      dp, am0, cval, cidx)
-  if (N <= 1024) {
-    if (pf) LG_NLL_ROWS(4, true);
-    else LG_NLL_ROWS(4, false);
-  } else if (N <= 2048) {
-    if (pf) LG_NLL_ROWS(8, true);
-    else LG_NLL_ROWS(8, false);
-  } else {
-    if (pf) LG_NLL_ROWS(16, true);
-    else LG_NLL_ROWS(16, false);
-  }
+  if (N <= 1024) LG_NLL_ROWS(4);
+  else if (N <= 2048) LG_NLL_ROWS(8);
+  else LG_NLL_ROWS(16);
 #undef LG_NLL_ROWS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

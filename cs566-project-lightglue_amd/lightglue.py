@@ -30,7 +30,6 @@ the NLL of each head into its head's backward (no dense d(loss)/d(log_assignment
 Gradients reach every parameter and both descriptor inputs.
 """
 import ctypes
-import os
 import warnings
 from pathlib import Path
 
@@ -292,15 +291,6 @@ class _Head(torch.autograd.Function):
         return (None, None, None, gd0, gd1, *grads)
 
 
-# env LG_HEAD_REUSE=0: the loss heads' backward recomputes md / z / similarity / LSEs (A/B runs)
-_HEAD_REUSE = os.environ.get("LG_HEAD_REUSE", "1") != "0"
-# env LG_HEAD_FUSED=0: the loss heads store their log assignment and take NLL / argmaxes from it
-_HEAD_FUSED = os.environ.get("LG_HEAD_FUSED", "1") != "0"
-# env LG_HEAD_GT=0: LightGlue.loss builds the dense [B, M+1, N+1] NLL weights (nll_weights) and the
-# heads' backward reads them, instead of reading the ground truth itself (lg_head_nll_backward)
-_HEAD_GT = os.environ.get("LG_HEAD_GT", "1") != "0"
-
-
 def _head_nll_forward(model, layer, d0, d1, params, tokens, prepared, balancing):
     """lg_head_nll_forward: head ``layer``'s NLL terms [5, B] and its log assignment's row / column
     argmaxes, the log assignment never stored; returns (terms, argmax0, argmax1, t0, t1, scratch)."""
@@ -332,20 +322,20 @@ class _HeadNLL(torch.autograd.Function):
     nll_pos, nll_neg, num_pos, num_neg, row argmax [B, M], column argmax [B, N] of the head's log
     assignment -- what TokenConfidence.loss compares, :108-122 -- token logits 0, token logits 1);
     the log assignment itself is never stored (lg_head_nll_forward).  The loss is linear in the log
-    assignment, so the backward hands lg_head_backward the weights and two per-pair scales instead
-    of a dense gradient."""
+    assignment, so the backward hands lg_head_nll_backward the ground truth (its NLL weights, never
+    built as a dense tensor) and two per-pair scales instead of a dense gradient."""
 
     @staticmethod
     def forward(ctx, model, layer, gt, balancing, tokens, d0, d1, *params):
         from .superglue import _nll
 
-        # gt = (data, NLLLoss weights [B, M+1, N+1] or None, nll_inputs(data)): built once per
-        # loss(); without the dense weights the backward reads them from nll_inputs' ground truth
-        data, w, prepared = gt
+        # gt = (data, nll_inputs(data)): built once per loss(); the backward reads the NLL weights
+        # from nll_inputs' ground truth
+        data, prepared = gt
         d0c, d1c = d0.float().contiguous(), d1.float().contiguous()
         # the scratch keeps md / z / similarity / LSEs for the backward (saved activations, ~1 GB per
         # head at configs[2]): no recompute of the head there (unless conf.checkpointed)
-        if _HEAD_FUSED and d1c.shape[1] <= 4096:
+        if d1c.shape[1] <= 4096:
             terms, am0, am1, t0, t1, scratch = _head_nll_forward(model, layer, d0c, d1c, params, tokens, prepared, balancing)
         else:
             la, _, t0, t1, scratch = _head_forward(model, layer, d0c, d1c, params, tokens, keep_scratch=True)
@@ -354,14 +344,14 @@ class _HeadNLL(torch.autograd.Function):
             del la
         # conf.checkpointed asks for activation memory over speed: the head's backward then
         # recomputes md / z / similarity / LSEs instead of keeping this ~1 GB scratch (configs[2])
-        ctx.scratch = scratch if (_HEAD_REUSE and not model.conf.checkpointed) else None
+        ctx.scratch = None if model.conf.checkpointed else scratch
         del scratch
         if not tokens:
             t0, t1 = d0c.new_zeros(0), d0c.new_zeros(0)
         ctx.model, ctx.layer, ctx.tokens, ctx.bal = model, layer, tokens, float(balancing)
-        ctx.gt = prepared if w is None else None
+        ctx.gt = prepared
         ctx.set_materialize_grads(False)  # unused outputs' gradients arrive as None, not zero tensors
-        ctx.save_for_backward(d0c, d1c, w, terms, *params)  # terms: never returned itself (clones below)
+        ctx.save_for_backward(d0c, d1c, terms, *params)  # terms: never returned itself (clones below)
         ctx.mark_non_differentiable(am0, am1)
         nll, pos, neg, npos, nneg = (terms[i].clone() for i in range(5))
         ctx.mark_non_differentiable(npos, nneg)
@@ -369,7 +359,7 @@ class _HeadNLL(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_nll, g_pos, g_neg, _g_npos, _g_nneg, _g_am0, _g_am1, g_t0, g_t1):
-        d0, d1, w, terms, *params = ctx.saved_tensors
+        d0, d1, terms, *params = ctx.saved_tensors
         npos, nneg = terms[3], terms[4]
 
         def lin(a, wa, c):  # a * wa + c, an absent (None: unused output) term left out
@@ -385,11 +375,11 @@ class _HeadNLL(torch.autograd.Function):
         if not ctx.tokens:
             g_t0 = g_t1 = None
         needs = list(ctx.needs_input_grad[7:]) + [ctx.needs_input_grad[5], ctx.needs_input_grad[6]]
-        gd0, gd1, grads = _head_backward(ctx.model, ctx.layer, d0, d1, params, needs, w, s_in, s_dust, None, g_t0, g_t1,
+        gd0, gd1, grads = _head_backward(ctx.model, ctx.layer, d0, d1, params, needs, None, s_in, s_dust, None, g_t0, g_t1,
                                          fwd_scratch=ctx.scratch, gt=ctx.gt)
         # only the forward's scratch is dropped (a second backward through a retained graph then
-        # recomputes the head); the ground truth stays: without the dense weights (w None) it is
-        # what the backward reads its NLL weights from
+        # recomputes the head); the ground truth stays: it is what the backward reads its NLL
+        # weights from
         ctx.scratch = None
         return (None, None, None, None, None, gd0, gd1, *grads)
 
@@ -915,18 +905,16 @@ class LightGlue(nn.Module):
         lconf = self.conf.loss
         if lconf.get("fn", "nll") != "nll":
             raise NotImplementedError(f"loss fn {lconf.fn!r} (the reference defines only 'nll')")
-        from .superglue import nll_inputs, nll_weights
+        from .superglue import nll_inputs
 
         bal = float(lconf.nll_balancing)
         rd0, rd1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
         N = rd0.shape[1]
         params = self._schema_params(rd0.device)
-        b, m, n = rd0.shape[0], rd0.shape[2], rd1.shape[2]
         # the ground truth's loss weights (losses.py:62-73) once, as the reference (gt_weights, :633);
-        # by default never as a dense [B, M+1, N+1] tensor: the heads' backward reads them from the
-        # ground truth (bit-identical, lg_head_nll_backward)
-        w = nll_weights(rd0.new_empty((b, m + 1, n + 1)), data) if not _HEAD_GT else None
-        gt = (data, w, nll_inputs(data, rd0.device))
+        # never as a dense [B, M+1, N+1] tensor: the heads' backward reads them from the ground truth
+        # (bit-identical to nll_weights, lg_head_nll_backward)
+        gt = (data, nll_inputs(data, rd0.device))
 
         sl0, sl1 = _LayerSlices.apply(rd0), _LayerSlices.apply(rd1)
 

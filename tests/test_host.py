@@ -275,3 +275,32 @@ def test_layer_slices_gradient_matches_indexing():
     b = rd.clone().requires_grad_()
     sum((b[:, i] * r[i]).sum() * (i + 1) for i in (0, 1, 3)).backward()
     assert torch.equal(a.grad, b.grad)
+
+
+def test_env_switches_are_documented():
+    """Every environment variable the library reads (getenv("...") in csrc) or the package reads
+    (os.environ / os.getenv in its *.py) is a row of DESIGN.md's table "Run-time switches the library
+    reads", and the table lists nothing else: an experiment's switch cannot stay behind unrecorded."""
+    pkg = os.path.join(ROOT, "cs566-project-lightglue_amd")
+    read = set()
+    for ext in ("hip", "cpp", "h"):
+        for f in glob.glob(os.path.join(pkg, "csrc", "*." + ext)):
+            read |= set(re.findall(r'getenv\(\s*"(\w+)"\s*\)', open(f).read()))
+    for f in glob.glob(os.path.join(pkg, "*.py")):
+        src = open(f).read()
+        read |= set(re.findall(r'os\.environ(?:\.get|\.setdefault|\.pop)?[\[(]\s*"(\w+)"', src))
+        read |= set(re.findall(r'os\.getenv\(\s*"(\w+)"', src))
+        read |= set(re.findall(r'"(\w+)"\s+(?:not\s+)?in\s+os\.environ', src))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    head = "**Run-time switches the library reads.**"
+    assert design.count(head) == 1
+    rows = []
+    for line in design[design.index(head):].split("\n")[1:]:
+        if line.startswith("|"):
+            rows.append(line)
+        elif rows:
+            break  # the table ends at the first line after it that is not a row
+    documented = {m.group(1) for m in (re.match(r"\|\s*`(\w+)`\s*\|", r) for r in rows[2:]) if m}
+    assert len(documented) == len(rows) - 2, "a row of the table does not start with one `NAME`"
+    assert read, "found no environment reads: the patterns no longer match the source"
+    assert read == documented, (sorted(read - documented), sorted(documented - read))

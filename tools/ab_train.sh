@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of training steps: bench.py --workload $WORKLOAD alternating over the variants given
 # as arguments, ROUNDS times.  A variant is a library path, optionally followed by env settings:
-#   bash tools/ab_train.sh ab/head.so ab/cur.so "ab/cur.so LG_TG_X6_FWD=0"
+#   bash tools/ab_train.sh ab/head.so ab/cur.so "ab/cur.so LG_SKF_EXACT=1"
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out

@@ -7,8 +7,8 @@ For every parameter (and the descriptor gradients): the GPU's max |g - g64| agai
 oracle, the reference's own float32 spread (stored in the golden) and the float32 ORACLE's spread
 (another plain fp32 implementation of the same step), the test bar 8 * spread32_ref + 1e-6 * max,
 and err / bar (the tests' bar: 8 x the larger of the reference's and the oracle's float32
-spreads; also against the reference's spread alone).  Run once per training arithmetic route (the LG_* / SG_* env switches are read once
-per process) to see which route moves which tensor.
+spreads; also against the reference's spread alone).  Each training product has one route; build a
+variant library and point LIGHTGLUE_MI355X_LIB at it to see which change moves which tensor.
 """
 import argparse
 import json

@@ -35,11 +35,11 @@ int main() {
   for (const Shape& s : shapes) {
     TGemm g{dY, X, dW, s.N, s.K, s.K, 0, 0, 0, s.N, s.K, R, 1, 1.f, 0.f, nullptr};
     g.colsumA = db;
-    CK(tgemm(g, true, false, ws, wsf, 0, 1));
+    CK(tgemm(g, true, false, ws, wsf, 0));
     CK(hipDeviceSynchronize());
     const int it = 10;
     CK(hipEventRecord(e0, 0));
-    for (int i = 0; i < it; ++i) CK(tgemm(g, true, false, ws, wsf, 0, 1));
+    for (int i = 0; i < it; ++i) CK(tgemm(g, true, false, ws, wsf, 0));
     CK(hipEventRecord(e1, 0));
     CK(hipEventSynchronize(e1));
     float ms = 0;
