@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LIGHTGLUE_MI355X_LIB", os.path.join(_HERE, "liblightglue_mi355x.so"))
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 LG_OK, LG_E_INVALID, LG_E_HIP, LG_E_WEIGHTS, LG_E_WORKSPACE, LG_E_INTERNAL = 0, -1, -2, -3, -4, -5
 
@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "lg_head_forward",
     "lg_train_gemm_workspace_bytes",
     "lg_train_gemm",
+    "lg_train_gemm_ex",
     "lg_train_attention",
     "lg_train_attention_backward",
     # SuperPoint extractor (include/superpoint_mi355x.h)
@@ -328,6 +329,12 @@ def load():
             ctypes.c_int,
             [_P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
              i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, _P, i32, i32, _P, sz, _P],
+        ),
+        "lg_train_gemm_ex": (
+            ctypes.c_int,
+            [_P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+             i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, _P, i32, i32,
+             _P, ctypes.c_int64, i32, _P, ctypes.c_int64, i32, _P, ctypes.c_int64, _P, _P, sz, _P],
         ),
         "lg_train_attention": (ctypes.c_int, [_P, _P, _P, i32, i32, i32, i32, ctypes.c_float, _P, _P, _P]),
         "lg_train_attention_backward": (

@@ -819,6 +819,29 @@ int lg_train_gemm(const float* A, const float* Bm, float* C, int64_t lda, int64_
   return LG_OK;
 }
 
+int lg_train_gemm_ex(const float* A, const float* Bm, float* C, int64_t lda, int64_t ldb, int64_t ldc, int64_t sA,
+                     int64_t sB, int64_t sC, int32_t M, int32_t N, int32_t K, int32_t batch, float alpha, float beta,
+                     const float* bias, int32_t ta, int32_t tb, const float* A1, int64_t lda1, int32_t K0, const float* B1,
+                     int64_t ldb1, int32_t N0, const float* R, int64_t ldr, float* colsumA, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  if (!A || !Bm || !C || M < 0 || N < 0 || K < 0 || batch < 0) return fail(LG_E_INVALID, "bad argument");
+  TGemm g{A, Bm, C, lda, ldb, ldc, sA, sB, sC, M, N, K, batch, alpha, beta, bias};
+  g.A1 = A1;
+  g.lda1 = lda1;
+  g.K0 = K0;
+  g.B1 = B1;
+  g.ldb1 = ldb1;
+  g.N0 = N0;
+  g.R = R;
+  g.ldr = ldr;
+  g.colsumA = colsumA;
+  const hipError_t e = tgemm(g, ta != 0, tb != 0, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(LG_E_INVALID, "no route of the training GEMM takes these operands");
+  TR_HIP(e);
+  TR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return LG_OK;
+}
+
 int lg_train_attention(const float* q, const float* k, const float* v, int32_t B, int32_t H, int32_t Nq, int32_t Nk,
                        float scale, float* o, float* lse, void* stream) {
   if (!q || !k || !v || !o || !lse || B < 0 || H <= 0 || H * 64 != D || Nq < 0 || Nk <= 0)

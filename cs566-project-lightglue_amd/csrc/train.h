@@ -7,7 +7,8 @@
 //     k-contiguous products (ta = 0) with K % 16 == 0 and 16-byte-aligned operands, every weight
 //     gradient (ta = 1, tb = 0), and the attention's S, P V, dP, dV and dK;
 //   * f32 MFMA (v_mfma_f32_32x32x2_f32 / 16x16x4_f32: exact fp32 products): tgemm's remaining shapes
-//     (K % 16 != 0, unaligned operands, ta && tb) and the attention backward's dQ, whose dS
+//     (K % 16 != 0, unaligned operands, beta outside {0, 1}, a beta term with batch > 1, an input
+//     gradient with batch > 1, ta && tb) and the attention backward's dQ, whose dS
 //     operand is already in LDS as fp32.
 // Reductions are deterministic (fixed-order partial sums) except the attention backward's dQ, which
 // is summed with float atomics.

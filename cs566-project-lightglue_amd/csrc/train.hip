@@ -2113,6 +2113,8 @@ static bool tgemm_x6(const TGemm& g, bool ta, bool tb, float* ws, size_t ws_floa
   x.res = g.R ? g.R : g.beta != 0.f ? g.C : nullptr;  // Y = res + (acc + bias) alpha
   x.ldr = (int)(g.R ? g.ldr : g.ldc);
   if (g.R && (g.beta != 1.f || g.batch != 1 || !al(g.R, g.ldr, 0))) return false;
+  // gemm_x6 reads `res` without a per-batch stride: a batched beta C would add batch 0's C everywhere
+  if (g.beta != 0.f && g.batch != 1 && !g.R) return false;
   x.Y = g.C;
   x.ldy = (int)g.ldc;
   x.out_scale = g.alpha;

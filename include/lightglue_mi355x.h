@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LG_ABI_VERSION 11
+#define LG_ABI_VERSION 12
 
 enum {
   LG_OK = 0,
@@ -333,9 +333,22 @@ int lg_head_nll_backward(lg_handle_t* h, const float* const* params, int32_t lay
                          float* grad_desc1, int32_t from_forward, void* scratch, size_t scratch_bytes, void* stream);
 
 /* Kernel-level entries of the training kernels (tests; no reference counterpart).
- * lg_train_gemm: C[b] = alpha (op(A[b]) op(B[b]) + bias) + beta C[b] on the f32 matrix cores,
- *   op(A)(m,k) = ta ? A[k*lda+m] : A[m*lda+k], op(B)(k,n) = tb ? B[n*ldb+k] : B[k*ldb+n];
- *   workspace: lg_train_gemm_workspace_bytes (split-k partials; 0 is allowed, then no split).
+ * lg_train_gemm: C[b] = alpha (op(A[b]) op(B[b]) + bias) + beta C[b] in fp32 with fp32
+ *   accumulation, op(A)(m,k) = ta ? A[k*lda+m] : A[m*lda+k], op(B)(k,n) = tb ? B[n*ldb+k] : B[k*ldb+n].
+ *   The route follows from shape and alignment alone: bf16x6 on the bf16 matrix cores (each fp32
+ *   operand split into three bf16 pieces; error per product ~2^-24) for ta = 0 with K % 16 == 0,
+ *   16-byte-aligned operands and beta in {0, 1} (beta = 0 when batch > 1; tb = 1 when batch > 1),
+ *   and for every weight gradient (ta = 1, tb = 0);
+ *   the f32 matrix cores for the remaining shapes.
+ *   workspace: lg_train_gemm_workspace_bytes (split-k partials with their column-sum partials, or
+ *   the transposed B of a (0, 0) product on the bf16x6 route; 0 is allowed, then no split and
+ *   (0, 0) on the f32 matrix cores).
+ * lg_train_gemm_ex: the same with the operands only the library's own calls pass (all nullable,
+ *   batch 1): A1 / lda1 / K0 (ta = 0, tb = 1 on the bf16x6 route: op(A)(m,k) = A1[m*lda1 + k - K0]
+ *   for k >= K0), B1 / ldb1 / N0 (ta = 1, tb = 0, N0 % 128 == 0, 16-byte-aligned operands:
+ *   op(B)(k,n) = B1[k*ldb1 + n - N0] for n >= N0), R / ldr (the beta term reads R instead of C;
+ *   R is not written) and colsumA [M] = sum_k op(A)(m,k) (ta = 1, tb = 0; ignored otherwise).
+ *   LG_E_INVALID, with nothing launched, when no route takes the operands.  ABI 12.
  * lg_train_attention / _backward: the fp32 training attention on fp32 head-major-in-columns
  *   tensors [B*Nq or B*Nk, 256] (head h at columns 64h..): O, lse [B*H*Nq] (log2 units); the
  *   backward writes dQ (zeroed first), dK, dV; delta_ws [B*H*Nq] floats.  Synchronise. */
@@ -343,6 +356,11 @@ int lg_train_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K, int32_t batch
 int lg_train_gemm(const float* A, const float* Bm, float* C, int64_t lda, int64_t ldb, int64_t ldc, int64_t sA,
                   int64_t sB, int64_t sC, int32_t M, int32_t N, int32_t K, int32_t batch, float alpha, float beta,
                   const float* bias, int32_t ta, int32_t tb, void* workspace, size_t workspace_bytes, void* stream);
+int lg_train_gemm_ex(const float* A, const float* Bm, float* C, int64_t lda, int64_t ldb, int64_t ldc, int64_t sA,
+                     int64_t sB, int64_t sC, int32_t M, int32_t N, int32_t K, int32_t batch, float alpha, float beta,
+                     const float* bias, int32_t ta, int32_t tb, const float* A1, int64_t lda1, int32_t K0, const float* B1,
+                     int64_t ldb1, int32_t N0, const float* R, int64_t ldr, float* colsumA, void* workspace,
+                     size_t workspace_bytes, void* stream);
 int lg_train_attention(const float* q, const float* k, const float* v, int32_t B, int32_t H, int32_t Nq, int32_t Nk,
                        float scale, float* o, float* lse, void* stream);
 int lg_train_attention_backward(const float* q, const float* k, const float* v, const float* o, const float* lse,

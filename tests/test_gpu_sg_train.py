@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import train_route_cases as rc
 from sg_golden_util import ground_truth
 from grad_golden_util import desc_golden, desc_pick
 from sg_grad_golden_util import golden_entries, load_sgtrain, oracle_sg_step, sgtrain_case, sgtrain_names
@@ -164,10 +165,13 @@ def test_sg_training_step_matches_reference_and_oracle(name):
     np.testing.assert_allclose(la, ola.numpy(), atol=max(1e-5, 8 * la_spread), rtol=0)
 
 
-@pytest.mark.parametrize("B,M,N,layers,iters", [(3, 50, 37, ["self", "cross"], 10), (1, 33, 70, ["cross"], 7)])
+@pytest.mark.parametrize("B,M,N,layers,iters", [(3, 50, 37, ["self", "cross"], 10), (1, 33, 70, ["cross"], 7),
+                                                rc.SG_UNFUSED, rc.SG_NOT_DEFERRED])
 def test_sg_training_step_ragged_against_oracle(B, M, N, layers, iters):
     """Shapes the goldens do not cover (odd sizes, M != N, B = 1 and 3) against the float64 oracle;
-    the bar's spread comes from the oracle's own float32 step."""
+    the bar's spread comes from the oracle's own float32 step.  The last two cases leave the fused
+    Sinkhorn (train_route_cases: N + 1 > 64 SKF_Q takes the unfused forward and backward,
+    iters > SKA_TMAX the fused backward that is not deferred)."""
     from lightglue_amd.sg_weights import superglue_state_dict, synthetic_scores
     from lightglue_amd.weights import synthetic_pair
 

@@ -304,3 +304,72 @@ def test_env_switches_are_documented():
     assert len(documented) == len(rows) - 2, "a row of the table does not start with one `NAME`"
     assert read, "found no environment reads: the patterns no longer match the source"
     assert read == documented, (sorted(read - documented), sorted(documented - read))
+
+
+def test_training_route_cases_reach_their_routes():
+    """The training kernels pick their route by shape alone, so the GPU tests reach a route only
+    through their shapes (tests/train_route_cases.py).  This reads every threshold out of the
+    launchers' source text and checks that each case lies on the side its comment claims; after a
+    threshold moves it fails and names the case to re-pick.  Constants only: no compiled output."""
+    import train_route_cases as rc
+
+    t = rc.thresholds()
+    # ---- tgemm: the bf16x6 route and its fallbacks
+    for c in rc.GEMM_CASES:
+        assert rc.x6_takes(t, c) == (c["route"] == "x6"), f"GEMM_CASES {c['name']}: re-pick ({c['why']})"
+    by = {c["name"]: c for c in rc.GEMM_CASES}
+    c = by["x6_ragged_tile"]
+    for dim, tile in ((c["M"], t["X6_TILE_M"]), (c["N"], t["X6_TILE_N"])):
+        assert dim > tile and dim % tile, "x6_ragged_tile: M and N need a full tile and a partial one"
+    assert by["x6_single_ktile"]["K"] == t["X6_TILE_K"] == t["X6_KMOD"], "x6_single_ktile: K must be one k-tile"
+    assert by["x6_padded_rows"]["pad"] % t["X6_LD"] == 0 and by["x6_padded_rows"]["pad"] > 0
+    for fb, x6 in (("f32_unaligned_a", "x6_ragged_tile"), ("f32_beta_half", "x6_ragged_tile"),
+                   ("f32_dgrad_batched", "x6_dgrad_transposed_weight"), ("f32_batched_beta_one", "x6_similarity")):
+        assert [by[fb][k] for k in "MNK"] == [by[x6][k] for k in "MNK"], f"{fb}: same shape as {x6}"
+    ex = rc.GEMM_EX
+    s = ex["a1"]
+    assert s["K"] % t["X6_KMOD"] == 0 and 0 < s["K0"] < s["K"] and s["K0"] % t["X6_KMOD"] == 0, "GEMM_EX a1: off bf16x6"
+    s = ex["b1_split"]
+    ks, kchunk = rc.tgemm_split(t, s["M"], s["N"], s["K"])
+    assert ks >= 2 and s["K"] % kchunk, f"GEMM_EX b1_split: {ks} chunks of {kchunk}: need a split with a partial last chunk"
+    nb = ctypes.c_size_t()  # the workspace entry covers the split's partials and their column-sum partials
+    assert _lib.load().lg_train_gemm_workspace_bytes(s["M"], s["N"], s["K"], 1, ctypes.byref(nb)) == 0
+    assert nb.value >= 4 * ks * s["M"] * (s["N"] + 1)
+    assert rc.tgemm_split(t, ex["b1_whole"]["M"], ex["b1_whole"]["N"], ex["b1_whole"]["K"])[0] == 1, "GEMM_EX b1_whole splits"
+    for k in ("b1_split", "b1_whole"):
+        assert ex[k]["M"] % 4 == 0 and ex[k]["N"] % 4 == 0 and ex[k]["N0"] % t["X6_BN"] == 0, f"GEMM_EX {k}: not the vector kernel"
+    assert ex["colsum_scalar"]["M"] % 4 or ex["colsum_scalar"]["N"] % 4, "GEMM_EX colsum_scalar takes the vector kernel"
+    assert ex["res_x6"]["K"] % t["X6_KMOD"] == 0 and ex["res_x6"]["K"] >= t["X6_KMIN"], "GEMM_EX res_x6: off bf16x6"
+    assert ex["res_f32"]["K"] % t["X6_KMOD"], "GEMM_EX res_f32: on bf16x6"
+    assert ex["refuse_a1"]["K"] % t["X6_KMOD"], "GEMM_EX refuse_a1: bf16x6 would take it"
+    assert ex["refuse_b1"]["N0"] % t["X6_BN"], "GEMM_EX refuse_b1: the vector kernel would take it"
+    # ---- assignment head
+    want = ["fused2", "fused4", "vector", "scalar"]
+    assert [rc.sim_lse_route(t, n) for _, _, n in rc.HEAD_DENSE] == want, "HEAD_DENSE: sim_lse routes moved"
+    assert [n > t["LA_NMAX"] for _, _, n in rc.HEAD_DENSE] == [False, False, True, True], "HEAD_DENSE: la_forward routes moved"
+    b, m, n = rc.HEAD_DENSE[0]
+    assert m > t["SLF_ROWS"] and m % t["SLF_ROWS"], "HEAD_DENSE[0]: M needs several SLF_ROWS blocks, the last partial"
+    assert all(m % t["LSE_ROWS"] for _, m, _ in rc.HEAD_DENSE[2:]), "HEAD_DENSE: unfused cases need a partial LSE_ROWS block"
+    r = b * (m + n)
+    assert r > t["HVG_ROWS"] and r % t["HVG_ROWS"], "HEAD_DENSE[0]: head_vec_grads needs several blocks, the last partial"
+    assert [rc._pick(t["NLL_KC"], n) for _, n in rc.HEAD_NLL] == [8, 16], "HEAD_NLL: la_nll variants moved"
+    assert [rc._pick(t["GT_IT"], n) for _, n in rc.HEAD_NLL] == [2, 4], "HEAD_NLL: la_grad_gt variants moved"
+    assert all(n % 4 == 0 and n <= t["LA_NMAX"] for _, n in rc.HEAD_NLL), "HEAD_NLL: off the vector kernels"
+    # ---- trunk and attention
+    conf, b, m, n = rc.TRUNK_MULTIBLOCK
+    r = b * (m + n)
+    for name in ("LN_ROWS", "PE_ROWS"):
+        assert r > 2 * t[name] and r % t[name], f"TRUNK_MULTIBLOCK: {name} needs several blocks, the last partial"
+    for out_rows, out_cols in ((768, 256), (256, 256), (512, 512), (256, 512)):  # the trunk's weight gradients
+        ks, kchunk = rc.tgemm_split(t, out_rows, out_cols, r)
+        assert ks >= 2 and r % kchunk, f"TRUNK_MULTIBLOCK: the {out_rows} x {out_cols} weight gradient is not split unevenly"
+    assert rc.colsum_chunks(t, rc.cdiv(r, t["LN_ROWS"]), 512) > 1, "TRUNK_MULTIBLOCK: lngelu_bwd's colsum is one chunk"
+    assert min(m, n) > max(t["ATTN_QBLOCK"], t["TB_KEYS"]), "TRUNK_MULTIBLOCK: attention within one block"
+    (_, q0, k0), (_, q1, k1) = rc.ATTN_MULTIBLOCK
+    assert q0 > t["ATTN_QBLOCK"] and k0 > 2 * t["TB_KEYS"], "ATTN_MULTIBLOCK[0]: within one query / key block"
+    assert q1 == t["ATTN_QBLOCK"] + 1 and k1 == 1, "ATTN_MULTIBLOCK[1]: one row into the second query block, one key"
+    # ---- SuperGlue training Sinkhorn
+    fused_max = 64 * t["SKF_Q"]
+    assert rc.SG_UNFUSED[2] + 1 > fused_max, "SG_UNFUSED: still fused"
+    assert rc.SG_UNFUSED[4] <= t["SKA_TMAX"]
+    assert rc.SG_NOT_DEFERRED[2] + 1 <= fused_max and rc.SG_NOT_DEFERRED[4] > t["SKA_TMAX"], "SG_NOT_DEFERRED: deferred or unfused"

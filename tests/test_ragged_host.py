@@ -15,11 +15,12 @@ import ragged_util as ru
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_abi_is_11():
+def test_library_abi_is_12():
+    """11 brought the ragged fields of lg_inputs_t, 12 lg_train_gemm_ex."""
     from lightglue_amd import _lib
 
     lib = _lib.load()
-    assert lib.lg_abi_version() == 11 == _lib.ABI_VERSION
+    assert lib.lg_abi_version() == 12 == _lib.ABI_VERSION
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
