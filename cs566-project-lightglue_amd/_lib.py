@@ -34,6 +34,9 @@ EXPORTED_SYMBOLS = [
     "lg_attention",
     "lg_assignment_workspace_bytes",
     "lg_assignment_head",
+    # homography ground truth (ABI 12, no handle)
+    "lg_gt_homography_workspace_bytes",
+    "lg_gt_matches_from_homography",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -301,6 +304,11 @@ def load():
         ),
         "lg_assignment_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_assignment_head": (ctypes.c_int, [_P, i32, _P, _P, i32, i32, i32, _P, _P, _P, _P, _P, sz, _P]),
+        "lg_gt_homography_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_matches_from_homography": (
+            ctypes.c_int,
+            [_P, _P, _P, i32, i32, i32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, sz, _P],
+        ),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_scratch_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),

@@ -450,4 +450,11 @@ size_t sg_nll_part_doubles(int B, int M);
 hipError_t sg_nll_loss(const float* la, int B, int M, int N, const uint8_t* gta, const int64_t* gt0, const int64_t* gt1,
                        int mode, float balancing, float* out, double* part, hipStream_t st);
 
+// Homography ground truth (gt_match.hip; gt_generation.py:109-161).  pos2 / neg2: the squared
+// thresholds as the fp32 values the reference compares against.  reward may be null.
+size_t gt_homography_workspace_bytes(int B, int M, int N);
+hipError_t gt_matches_from_homography(const float* kp0, const float* kp1, const float* H, int B, int M, int N, float pos2,
+                                      float neg2, uint8_t* assignment, float* reward, int64_t* m0, int64_t* m1, float* s0,
+                                      float* s1, float* p01, float* p10, void* workspace, hipStream_t st);
+
 }  // namespace lg

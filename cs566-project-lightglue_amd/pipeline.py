@@ -5,16 +5,20 @@ model registry that resolve the matcher by name.
   (``models/__init__.py:7-30``): ``"matchers.lightglue"`` (and ``"lightglue"``) resolve to the HIP
   :class:`~lightglue_amd.lightglue.LightGlue` (the reference module's ``__main_model__``,
   ``lightglue.py:666``); ``"matchers.lightglue_pretrained_MINE"`` to the wrapper below;
-  ``"two_view_pipeline"`` to :class:`TwoViewPipeline`.  Other components (extractors, filters,
+  ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
+  HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
   ``data`` unchanged.
-* :class:`TwoViewPipeline` — ``models/two_view_pipeline.py:21-97``: extractor per view (or the
+* :class:`TwoViewPipeline` — ``models/two_view_pipeline.py:21-121``: extractor per view (or the
   view's ``cache`` when ``allow_no_extract``), then matcher / filter / solver, each called on the
-  merged dict ``{**data, **pred}`` and its outputs merged into ``pred``.
+  merged dict ``{**data, **pred}`` and its outputs merged into ``pred``; ``loss`` runs the
+  ``ground_truth`` component and sums the components' losses, which is what the reference's trainer
+  calls (``train.py``: ``loss_fn = model.loss``).
 
-Plain host-side plumbing: no arithmetic happens here; the matcher's forward is the HIP path.
+Plain host-side plumbing: no arithmetic happens here beyond summing the components' totals; the
+components' forward, loss and backward are the HIP paths.
 """
 from torch import nn
 
@@ -62,7 +66,7 @@ class BaseModel(nn.Module):
         return self._forward(data)
 
     def loss(self, pred, data):
-        raise NotImplementedError("training is out of scope for the MI355X matcher (SURVEY.md §2)")
+        raise NotImplementedError
 
 
 class LightGluePreTrainedMINE(BaseModel):
@@ -77,9 +81,12 @@ class LightGluePreTrainedMINE(BaseModel):
     def _forward(self, data):
         return self.net(data)
 
+    def loss(self, pred, data):
+        return self.net.loss(pred, data)
+
 
 class TwoViewPipeline(BaseModel):
-    """models/two_view_pipeline.py:21-97 (the eval path; ground-truth and loss are training-side)."""
+    """models/two_view_pipeline.py:21-121."""
 
     default_conf = {
         "extractor": {"name": None, "trainable": False},
@@ -120,6 +127,34 @@ class TwoViewPipeline(BaseModel):
             pred.update({f"gt_{k}": v for k, v in gt_pred.items()})
         return pred
 
+    def loss(self, pred, data):  # :99-121
+        losses = {}
+        metrics = {}
+        total = 0
+
+        # get labels
+        if self.conf.ground_truth.name and not self.conf.run_gt_in_forward:
+            gt_pred = self.ground_truth({**data, **pred})
+            pred.update({f"gt_{k}": v for k, v in gt_pred.items()})
+
+        for k in self.components:
+            apply = True
+            if "apply_loss" in self.conf[k].keys():
+                apply = self.conf[k].apply_loss
+            if self.conf[k].name and apply:
+                try:
+                    out = getattr(self, k).loss(pred, {**pred, **data})
+                except NotImplementedError:
+                    continue
+                # the reference unpacks (losses, metrics) here, which its own SuperGlue.loss
+                # (superglue.py:309-339, a bare dict of losses) does not survive: a dict is taken as
+                # the losses with no metrics
+                losses_, metrics_ = (out, {}) if isinstance(out, dict) else out
+                losses = {**losses, **losses_}
+                metrics = {**metrics, **metrics_}
+                total = losses_["total"] + total
+        return {**losses, "total": total}, metrics
+
 
 def _superpoint():
     from .superpoint import SuperPoint
@@ -131,6 +166,12 @@ def _superglue():
     from .superglue import SuperGlue
 
     return SuperGlue
+
+
+def _homography_matcher():
+    from .gt_matcher import HomographyMatcher
+
+    return HomographyMatcher
 
 
 _REGISTRY = {
@@ -146,6 +187,9 @@ _REGISTRY = {
     # the SuperGlue matcher (gluefactory_nonfree/superglue.py), resolved lazily
     "gluefactory_nonfree.superglue": _superglue,
     "superglue": _superglue,
+    # the homography ground truth (matchers/homography_matcher.py), resolved lazily
+    "matchers.homography_matcher": _homography_matcher,
+    "homography_matcher": _homography_matcher,
 }
 
 
@@ -160,7 +204,7 @@ def get_model(name):
     for path in (name, f"matchers.{name}", f"extractors.{name}"):
         if path in _REGISTRY:
             obj = _REGISTRY[path]
-            return obj() if obj in (_superpoint, _superglue) else obj
+            return obj() if obj in (_superpoint, _superglue, _homography_matcher) else obj
     paths = [name, f"gluefactory.models.{name}", f"gluefactory.models.extractors.{name}",
              f"gluefactory.models.matchers.{name}"]
     raise RuntimeError(f'Model {name} not found in any of [{" ".join(paths)}]')

@@ -213,6 +213,28 @@ int lg_log_optimal_transport(const float* scores, float alpha, int32_t B, int32_
                              int32_t iters, float* Z, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Homography ground truth: gt_matches_from_homography (gluefactory/geometry/gt_generation.py:109-161
+ * with warp_points_torch, geometry/homography.py:161-180), what matchers.homography_matcher computes
+ * for TwoViewPipeline.loss.  Added under ABI 12 (two new entries, nothing else changes).  No handle.
+ * Device inputs kp0 [B,M,2], kp1 [B,N,2], H [B,3,3], fp32; pos_th / neg_th are the reference's
+ * th_positive / th_negative in pixels (squared in double, then compared in fp32, as the reference).
+ * Device outputs: assignment_u8 [B,M,N] 0/1 (a torch.bool tensor's bytes), reward_or_null [B,M,N]
+ * fp32 (NULL: not computed), matches0 [B,M] / matches1 [B,N] int64 (-1 unmatched, -2 ignored),
+ * scores0/1 = (matches > -1) as fp32, proj_0to1 [B,M,2] = kp0 through H, proj_1to0 [B,N,2] = kp1
+ * through H^-1.  H^-1 is formed on the device: the adjugate over the determinant of the fp32 H in
+ * fp64, rounded once to fp32; a singular H is outside the contract (results undefined, no error).
+ * Equal minima resolve to the lowest index, as torch.min; no atomics, identical results run to run.
+ * Nothing of size M*N is kept besides the outputs; workspace (lg_gt_homography_workspace_bytes) is
+ * 12 bytes per keypoint.  Stream-ordered, asynchronous.  LG_E_INVALID: a null pointer, a negative
+ * size, M * N >= 2^31, a short workspace, a pointer off its natural alignment (8 bytes for the
+ * keypoints, projections and matches: one point / one index; 4 for the rest).  B, M or N == 0: LG_OK, nothing launched, no output
+ * written. */
+int lg_gt_homography_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes);
+int lg_gt_matches_from_homography(const float* kp0, const float* kp1, const float* H, int32_t B, int32_t M, int32_t N,
+                                  double pos_th, double neg_th, uint8_t* assignment_u8, float* reward_or_null,
+                                  int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* proj_0to1,
+                                  float* proj_1to0, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
