@@ -37,6 +37,9 @@ EXPORTED_SYMBOLS = [
     # homography ground truth (ABI 12, no handle)
     "lg_gt_homography_workspace_bytes",
     "lg_gt_matches_from_homography",
+    # pose-and-depth ground truth (ABI 12, no handle)
+    "lg_gt_depth_workspace_bytes",
+    "lg_gt_matches_from_pose_depth",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -308,6 +311,12 @@ def load():
         "lg_gt_matches_from_homography": (
             ctypes.c_int,
             [_P, _P, _P, i32, i32, i32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, sz, _P],
+        ),
+        "lg_gt_depth_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_matches_from_pose_depth": (
+            ctypes.c_int,
+            [_P, _P, _P, i32, i32, _P, i32, i32, _P, _P, i32, _P, _P, i32, i32, i32] + [ctypes.c_double] * 4
+            + [_P] * 15 + [sz, _P],
         ),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),

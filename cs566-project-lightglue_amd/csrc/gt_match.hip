@@ -18,6 +18,10 @@
 //                16-byte stores over each pair's flat [M*N] block behind a scalar head up to the
 //                first 16-byte boundary (odd N, unaligned pair bases)
 //
+// The scan of gt_stats, gt_fill0, gt_finalize and the flat writer of gt_reward are the templates of
+// gt_common.h, shared with the pose-and-depth ground truth (gt_depth.hip); this file supplies the
+// homography arithmetic they run.
+//
 // This TU is built with -ffp-contract=off (Makefile): every subtraction, product and sum of a distance
 // is rounded on its own, as the reference's separate torch passes do, and pass 1 and the write pass
 // get the same bits for the same (i, j).
@@ -25,21 +29,13 @@
 
 #include <cstdint>
 
+#include "gt_common.h"
 #include "kernels.h"
 
 namespace lg {
 namespace {
 
-constexpr int kOwn = 64;      // owned points per workgroup (one per lane)
-constexpr int kWaves = 4;     // waves per workgroup, each scans a quarter of a staged chunk
-constexpr int kChunk = 1024;  // staged points per chunk: 16 KiB of LDS
-
-// |a - b|^2 as torch.sum((a - b) ** 2, -1): four roundings.  (a - b) and (b - a) differ by sign only,
-// so the value does not depend on the operand order.
-__device__ __forceinline__ float sqd(float ax, float ay, float bx, float by) {
-  const float dx = ax - bx, dy = ay - by;
-  return dx * dx + dy * dy;
-}
+using namespace gt;
 
 // dist(i, j) and its two halves from point i of image 0 (raw a, projected pa = kp0_1[i]) and point j
 // of image 1 (raw b, projected pb = kp1_0[j]): dist0 = |pa - b|^2, dist1 = |a - pb|^2 (:124-126)
@@ -102,18 +98,30 @@ __global__ __launch_bounds__(256) void gt_project(const float* __restrict__ kp0,
 // Pass 1.  Blocks [0, B * bm) own rows (points of image 0, scanning image 1), the rest own columns.
 // With u = |proj(own) - raw(other)|^2 and v = |raw(own) - proj(other)|^2: a row has dist0 = u,
 // dist1 = v; a column has dist1 = u, dist0 = v (sqd is symmetric).  Either way dist = max(u, v) and the
-// third statistic is min u, so one body serves both directions.
+// third statistic is min u, so one body serves both directions (gt_common.h: scan).
+struct HomographyScan {
+  static constexpr bool kFlag = false;
+  struct Own {
+    float x, y, px, py;
+  };
+  const float2 *oth_raw, *oth_prj;
+  __device__ __forceinline__ float4 stage(int q, uint8_t&) const {
+    const float2 r = oth_raw[q], pr = oth_prj[q];
+    return make_float4(r.x, r.y, pr.x, pr.y);
+  }
+  __device__ __forceinline__ void eval(const Own& o, float4 s, uint8_t, float& d, float& u) const {
+    u = sqd(o.px, o.py, s.x, s.y);
+    const float v = sqd(o.x, o.y, s.z, s.w);
+    d = fmaxf(u, v);
+  }
+};
+
 __global__ __launch_bounds__(kOwn* kWaves) void gt_stats(const float* __restrict__ kp0, const float* __restrict__ kp1,
                                                          const float* __restrict__ p01, const float* __restrict__ p10,
                                                          int B, int M, int N, int bm, int bn,
                                                          float* __restrict__ rmin, int* __restrict__ rarg,
                                                          float* __restrict__ rmin0, float* __restrict__ cmin,
                                                          int* __restrict__ carg, float* __restrict__ cmin1) {
-  __shared__ float4 stage[kChunk];
-  __shared__ float pmin[kWaves][kOwn];
-  __shared__ float pthird[kWaves][kOwn];
-  __shared__ int parg[kWaves][kOwn];
-
   int blk = blockIdx.x;
   const bool cols = blk >= B * bm;
   if (cols) blk -= B * bm;
@@ -122,63 +130,21 @@ __global__ __launch_bounds__(kOwn* kWaves) void gt_stats(const float* __restrict
   const int P = cols ? N : M, Q = cols ? M : N;  // owned side, scanned side
   const float* own_raw = (cols ? kp1 : kp0) + (size_t)b * P * 2;
   const float* own_prj = (cols ? p10 : p01) + (size_t)b * P * 2;
-  const float* oth_raw = (cols ? kp0 : kp1) + (size_t)b * Q * 2;
-  const float* oth_prj = (cols ? p01 : p10) + (size_t)b * Q * 2;
+  HomographyScan op;
+  op.oth_raw = reinterpret_cast<const float2*>((cols ? kp0 : kp1) + (size_t)b * Q * 2);
+  op.oth_prj = reinterpret_cast<const float2*>((cols ? p01 : p10) + (size_t)b * Q * 2);
 
-  const int lane = threadIdx.x & (kOwn - 1), wave = threadIdx.x / kOwn;
+  const int lane = threadIdx.x & (kOwn - 1);
   const int p = (blk - b * per) * kOwn + lane;
   const bool live = p < P;
-  float ox = 0.f, oy = 0.f, opx = 0.f, opy = 0.f;
+  HomographyScan::Own own = {0.f, 0.f, 0.f, 0.f};
   if (live) {
     const float2 r = reinterpret_cast<const float2*>(own_raw)[p], q = reinterpret_cast<const float2*>(own_prj)[p];
-    ox = r.x;
-    oy = r.y;
-    opx = q.x;
-    opy = q.y;
+    own = {r.x, r.y, q.x, q.y};
   }
-  float best = __builtin_inff(), third = __builtin_inff();
-  int arg = 0;
-  constexpr int kQuarter = kChunk / kWaves;
-  for (int q0 = 0; q0 < Q; q0 += kChunk) {
-    const int cnt = min(kChunk, Q - q0);
-    __syncthreads();  // the previous chunk is fully read
-    for (int t = threadIdx.x; t < cnt; t += kOwn * kWaves) {
-      const int q = q0 + t;
-      const float2 r = reinterpret_cast<const float2*>(oth_raw)[q], pr = reinterpret_cast<const float2*>(oth_prj)[q];
-      stage[t] = make_float4(r.x, r.y, pr.x, pr.y);
-    }
-    __syncthreads();
-    const int t1 = min(cnt, (wave + 1) * kQuarter);
-#pragma unroll 4
-    for (int t = wave * kQuarter; t < t1; ++t) {  // ascending, strict <: the first minimum stays
-      const float4 s = stage[t];
-      const float u = sqd(opx, opy, s.x, s.y);
-      const float v = sqd(ox, oy, s.z, s.w);
-      const float d = fmaxf(u, v);
-      if (d < best) {
-        best = d;
-        arg = q0 + t;
-      }
-      third = fminf(third, u);
-    }
-  }
-  pmin[wave][lane] = best;
-  parg[wave][lane] = arg;
-  pthird[wave][lane] = third;
-  __syncthreads();
-  if (wave == 0 && live) {
-    // a wave's indices ascend within a chunk but interleave with the other waves' across chunks:
-    // equal minima resolve to the lowest index explicitly
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) {
-      const float m = pmin[w][lane];
-      const int a = parg[w][lane];
-      if (m < best || (m == best && a < arg)) {
-        best = m;
-        arg = a;
-      }
-      third = fminf(third, pthird[w][lane]);
-    }
+  float best, third;
+  int arg;
+  if (scan(op, own, Q, best, arg, third) && live) {
     const size_t o = (size_t)b * P + p;
     (cols ? cmin : rmin)[o] = best;
     (cols ? carg : rarg)[o] = arg;
@@ -186,102 +152,36 @@ __global__ __launch_bounds__(kOwn* kWaves) void gt_stats(const float* __restrict
   }
 }
 
-// Zeros over n bytes: a scalar head up to the first 16-byte boundary, uint4 stores, a scalar tail.
-__global__ __launch_bounds__(256) void gt_fill0(uint8_t* __restrict__ dst, size_t n) {
-  const size_t head = min(n, (size_t)((16 - ((uintptr_t)dst & 15)) & 15));
-  const size_t nvec = (n - head) / 16;
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  uint4* v = reinterpret_cast<uint4*>(dst + head);
-  for (size_t k = tid; k < nvec; k += stride) v[k] = make_uint4(0, 0, 0, 0);
-  if (tid < head) dst[tid] = 0;
-  const size_t tail0 = head + nvec * 16;
-  if (tail0 + tid < n) dst[tail0 + tid] = 0;  // fewer than 16 bytes
-}
-
-// matches / scores of both sides (:139-158) and the ones of `positive` (:137).  positive[i, j] needs
-// j = argmin_row[i], argmin_col[j] = i and dist(i, j) < pos2, and dist(i, argmin_row[i]) is rmin[i].
-__global__ __launch_bounds__(256) void gt_finalize(const float* __restrict__ rmin, const int* __restrict__ rarg,
-                                                   const float* __restrict__ rmin0, const float* __restrict__ cmin,
-                                                   const int* __restrict__ carg, const float* __restrict__ cmin1, int B,
-                                                   int M, int N, float pos2, float neg2, uint8_t* __restrict__ assignment,
-                                                   int64_t* __restrict__ m0, int64_t* __restrict__ m1,
-                                                   float* __restrict__ s0, float* __restrict__ s1) {
-  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t nr = (size_t)B * M, nc = (size_t)B * N;
-  if (t < nr) {
-    const size_t b = t / M;
-    const int i = (int)(t - b * M), j = rarg[t];
-    const bool pos = carg[b * N + j] == i && rmin[t] < pos2;
-    int64_t m = pos ? (int64_t)j : -2;
-    if (rmin0[t] > neg2) m = -1;
-    m0[t] = m;
-    s0[t] = m > -1 ? 1.f : 0.f;
-    if (pos) assignment[(b * M + i) * N + j] = 1;
-  } else if (t < nr + nc) {
-    const size_t c = t - nr, b = c / N;
-    const int j = (int)(c - b * N), i = carg[c];
-    const bool pos = rarg[b * M + i] == j && cmin[c] < pos2;
-    int64_t m = pos ? (int64_t)i : -2;
-    if (cmin1[c] > neg2) m = -1;
-    m1[c] = m;
-    s1[c] = m > -1 ? 1.f : 0.f;
+// reward (:128): (dist < pos_th^2) - (dist > neg_th^2) with dist recomputed by the same expression
+// (gt_common.h: write_flat).  Keypoints as 8-byte loads (the API checks the alignment).
+struct HomographyReward {
+  struct Row {
+    float2 a, pa;
+  };
+  const float2 *a2, *pa2, *b2, *pb2;
+  float pos2, neg2;
+  __device__ __forceinline__ Row row(unsigned i) const { return {a2[i], pa2[i]}; }
+  __device__ __forceinline__ float value(const Row& r, unsigned j) const {
+    const float2 cb = b2[j], cpb = pb2[j];
+    const float d = pair_dist(r.a.x, r.a.y, r.pa.x, r.pa.y, cb.x, cb.y, cpb.x, cpb.y).d;
+    return (d < pos2 ? 1.f : 0.f) - (d > neg2 ? 1.f : 0.f);
   }
-}
+};
 
-// reward (:128).  Pair b's block is a flat run of MN floats; thread g owns the four entries from
-// head + 4 g, where head is the distance to the first 16-byte boundary, and thread 0 also writes the head.
 __global__ __launch_bounds__(256) void gt_reward(const float* __restrict__ kp0, const float* __restrict__ kp1,
                                                  const float* __restrict__ p01, const float* __restrict__ p10, int M, int N,
                                                  unsigned bpp, float pos2, float neg2, float* __restrict__ reward) {
   const unsigned b = blockIdx.x / bpp;
   const unsigned g = (blockIdx.x - b * bpp) * 256u + threadIdx.x;
-  const unsigned MN = (unsigned)M * (unsigned)N;
-  float* out = reward + (size_t)b * MN;
-  const float* a = kp0 + (size_t)b * M * 2;
-  const float* pa = p01 + (size_t)b * M * 2;
-  const float* bq = kp1 + (size_t)b * N * 2;
-  const float* pb = p10 + (size_t)b * N * 2;
-  // keypoints as 8-byte loads (the API checks the alignment); the row's point is reloaded only
-  // where the flat run wraps into the next row
-  const float2* a2 = reinterpret_cast<const float2*>(a);
-  const float2* pa2 = reinterpret_cast<const float2*>(pa);
-  const float2* b2 = reinterpret_cast<const float2*>(bq);
-  const float2* pb2 = reinterpret_cast<const float2*>(pb);
-  auto value = [&](float2 ra, float2 rpa, unsigned j) {
-    const float2 cb = b2[j], cpb = pb2[j];
-    const float d = pair_dist(ra.x, ra.y, rpa.x, rpa.y, cb.x, cb.y, cpb.x, cpb.y).d;
-    return (d < pos2 ? 1.f : 0.f) - (d > neg2 ? 1.f : 0.f);
-  };
-  const unsigned head = min(MN, (unsigned)(((16 - ((uintptr_t)out & 15)) & 15) >> 2));
-  if (g == 0)
-    for (unsigned r = 0; r < head; ++r) out[r] = value(a2[r / N], pa2[r / N], r % N);
-  const unsigned long long r0 = head + 4ull * g;
-  if (r0 >= MN) return;
-  unsigned i = (unsigned)r0 / (unsigned)N, j = (unsigned)r0 - i * (unsigned)N;
-  const unsigned left = MN - (unsigned)r0;
-  float2 ra = a2[i], rpa = pa2[i];
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if ((unsigned)k < left) {
-      v[k] = value(ra, rpa, j);
-      if (++j == (unsigned)N) {
-        j = 0;
-        if (++i < (unsigned)M) {
-          ra = a2[i];
-          rpa = pa2[i];
-        }
-      }
-    }
-  }
-  if (left >= 4) {
-    *reinterpret_cast<float4*>(out + r0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (unsigned k = 0; k < left; ++k) out[r0 + k] = v[k];
-  }
+  HomographyReward op;
+  op.a2 = reinterpret_cast<const float2*>(kp0 + (size_t)b * M * 2);
+  op.pa2 = reinterpret_cast<const float2*>(p01 + (size_t)b * M * 2);
+  op.b2 = reinterpret_cast<const float2*>(kp1 + (size_t)b * N * 2);
+  op.pb2 = reinterpret_cast<const float2*>(p10 + (size_t)b * N * 2);
+  op.pos2 = pos2;
+  op.neg2 = neg2;
+  write_flat(op, reward + (size_t)b * (unsigned)M * (unsigned)N, (unsigned)M, (unsigned)N, g);
 }
-
-size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
 
 }  // namespace
 
@@ -307,12 +207,10 @@ hipError_t gt_matches_from_homography(const float* kp0, const float* kp1, const 
   const int bm = (M + kOwn - 1) / kOwn, bn = (N + kOwn - 1) / kOwn;
   gt_stats<<<dim3((unsigned)B * (bm + bn)), dim3(kOwn * kWaves), 0, st>>>(kp0, kp1, p01, p10, B, M, N, bm, bn, rmin, rarg,
                                                                          rmin0, cmin, carg, cmin1);
-  const size_t nbytes = (size_t)B * M * N;
-  const size_t fill_blocks = (nbytes / 16 + 255) / 256 + 1;
-  gt_fill0<<<dim3((unsigned)(fill_blocks < 65536 ? fill_blocks : 65536)), dim3(256), 0, st>>>(assignment, nbytes);
+  launch_fill0(assignment, (size_t)B * M * N, st);
   const size_t nfin = (size_t)B * M + (size_t)B * N;
-  gt_finalize<<<dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, st>>>(rmin, rarg, rmin0, cmin, carg, cmin1, B, M, N, pos2,
-                                                                        neg2, assignment, m0, m1, s0, s1);
+  gt_finalize<false><<<dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, st>>>(
+      rmin, rarg, rmin0, cmin, carg, cmin1, B, M, N, pos2, neg2, assignment, m0, m1, s0, s1, nullptr, nullptr, nullptr, nullptr);
   if (reward) {
     const unsigned rpp = (unsigned)(((size_t)M * N / 4 + 1 + 255) / 256);
     gt_reward<<<dim3((unsigned)B * rpp), dim3(256), 0, st>>>(kp0, kp1, p01, p10, M, N, rpp, pos2, neg2, reward);

@@ -457,4 +457,24 @@ hipError_t gt_matches_from_homography(const float* kp0, const float* kp1, const 
                                       float neg2, uint8_t* assignment, float* reward, int64_t* m0, int64_t* m1, float* s0,
                                       float* s1, float* p01, float* p10, void* workspace, hipStream_t st);
 
+// Pose-and-depth ground truth (gt_depth.hip; gt_generation.py:13-106).  Thresholds as the fp32 values
+// the reference compares against: pos2 / neg2 squared, negf (the epipolar bound) and ccth plain.
+// valid_in0/1 not null: dk0/1 and they are the caller's depths (inputs); null: dk0/1 are outputs,
+// sampled from the maps.  reward may be null.
+struct GtDepthCall {
+  const float *kp0, *kp1, *depth0, *depth1, *cam0, *cam1, *T_0to1, *T_1to0;
+  int H0, W0, H1, W1, n_dist, B, M, N;
+  float pos2, neg2, negf, ccth;
+  bool use_epi, use_cc;
+  float *dk0, *dk1;
+  const uint8_t *valid_in0, *valid_in1;
+  uint8_t* assignment;
+  float* reward;
+  int64_t *m0, *m1;
+  float *s0, *s1, *p01, *p10;
+  uint8_t *vis0, *vis1;
+};
+size_t gt_depth_workspace_bytes(int B, int M, int N);
+hipError_t gt_matches_from_pose_depth(const GtDepthCall& c, void* workspace, hipStream_t st);
+
 }  // namespace lg

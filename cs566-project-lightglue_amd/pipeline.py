@@ -6,7 +6,8 @@ model registry that resolve the matcher by name.
   :class:`~lightglue_amd.lightglue.LightGlue` (the reference module's ``__main_model__``,
   ``lightglue.py:666``); ``"matchers.lightglue_pretrained_MINE"`` to the wrapper below;
   ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
-  HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`).  Other components (filters,
+  HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.depth_matcher"`` to the
+  pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -174,6 +175,14 @@ def _homography_matcher():
     return HomographyMatcher
 
 
+def _depth_matcher():
+    from .depth_matcher import DepthMatcher
+
+    return DepthMatcher
+
+
+_LAZY = (_superpoint, _superglue, _homography_matcher, _depth_matcher)
+
 _REGISTRY = {
     "lightglue": LightGlue,
     "matchers.lightglue": LightGlue,
@@ -190,6 +199,9 @@ _REGISTRY = {
     # the homography ground truth (matchers/homography_matcher.py), resolved lazily
     "matchers.homography_matcher": _homography_matcher,
     "homography_matcher": _homography_matcher,
+    # the pose-and-depth ground truth (matchers/depth_matcher.py), resolved lazily
+    "matchers.depth_matcher": _depth_matcher,
+    "depth_matcher": _depth_matcher,
 }
 
 
@@ -204,7 +216,7 @@ def get_model(name):
     for path in (name, f"matchers.{name}", f"extractors.{name}"):
         if path in _REGISTRY:
             obj = _REGISTRY[path]
-            return obj() if obj in (_superpoint, _superglue, _homography_matcher) else obj
+            return obj() if obj in _LAZY else obj
     paths = [name, f"gluefactory.models.{name}", f"gluefactory.models.extractors.{name}",
              f"gluefactory.models.matchers.{name}"]
     raise RuntimeError(f'Model {name} not found in any of [{" ".join(paths)}]')

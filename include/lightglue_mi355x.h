@@ -235,6 +235,38 @@ int lg_gt_matches_from_homography(const float* kp0, const float* kp1, const floa
                                   int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* proj_0to1,
                                   float* proj_1to0, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Pose-and-depth ground truth: gt_matches_from_pose_depth (gluefactory/geometry/gt_generation.py:13-106
+ * with sample_depth / project, geometry/depth.py, the Camera / Pose rows of geometry/wrappers.py and
+ * sym_epipolar_distance_all, geometry/epipolar.py:59-72), what matchers.depth_matcher computes.  Two
+ * more entries under ABI 12.  No handle.  Device inputs, fp32: kp0 [B,M,2], kp1 [B,N,2]; depth0
+ * [B,H0,W0], depth1 [B,H1,W1] (values <= 0 mean "no depth"); cam0 / cam1 [B, 6 + n_dist] rows
+ * (w, h, fx, fy, cx, cy, then k1, k2 with n_dist >= 2, then p1, p2 with n_dist == 4); T_0to1 / T_1to0
+ * [B,12] rows (R row-major, then t).  pos_th / neg_th: th_positive / th_negative in pixels.
+ * th_epi_or_nan / th_consistency_or_nan: NaN means None.  th_epi only switches the epipolar step on
+ * (the reference compares against neg_th there); th_consistency is compared with the squared
+ * round-trip distance, as the reference does.
+ * valid_depth0/1_or_null both null: depth_keypoints0/1 [B,M] / [B,N] are outputs, sampled from the
+ * maps.  Both given (uint8 0/1): depth_keypoints0/1 and they are the caller's precomputed depths and
+ * the maps may be null, unless th_consistency is set.
+ * Device outputs: those of lg_gt_matches_from_homography plus visible0_u8 [B,M], visible1_u8 [B,N]
+ * (torch.bool bytes).  reward = (dist < pos_th^2) - (epi > neg_th), dist masked by visibility.
+ * F is formed on the device in fp64 from the fp32 rows and rounded once.  No atomics, identical
+ * results run to run, nothing of size M*N besides the outputs; workspace
+ * (lg_gt_depth_workspace_bytes) is about 34 bytes per keypoint and must be 16-byte aligned.
+ * Stream-ordered, asynchronous.  LG_E_INVALID: a null pointer, a negative size, M * N >= 2^31, a
+ * short workspace, a pointer off its natural alignment (as above), n_dist outside {0, 2, 4}, a null
+ * or empty depth map where one is needed.  B, M or N == 0: LG_OK, nothing launched, no output written. */
+int lg_gt_depth_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes);
+int lg_gt_matches_from_pose_depth(const float* kp0, const float* kp1, const float* depth0_or_null, int32_t H0, int32_t W0,
+                                  const float* depth1_or_null, int32_t H1, int32_t W1, const float* cam0, const float* cam1,
+                                  int32_t n_dist, const float* T_0to1, const float* T_1to0, int32_t B, int32_t M, int32_t N,
+                                  double pos_th, double neg_th, double th_epi_or_nan, double th_consistency_or_nan,
+                                  float* depth_keypoints0, float* depth_keypoints1, const uint8_t* valid_depth0_or_null,
+                                  const uint8_t* valid_depth1_or_null, uint8_t* assignment_u8, float* reward_or_null,
+                                  int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* proj_0to1,
+                                  float* proj_1to0, uint8_t* visible0_u8, uint8_t* visible1_u8, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
