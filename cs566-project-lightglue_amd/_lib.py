@@ -40,6 +40,9 @@ EXPORTED_SYMBOLS = [
     # pose-and-depth ground truth (ABI 12, no handle)
     "lg_gt_depth_workspace_bytes",
     "lg_gt_matches_from_pose_depth",
+    # nearest-neighbour matcher (ABI 12, no handle)
+    "lg_nn_workspace_bytes",
+    "lg_nn_match",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -317,6 +320,11 @@ def load():
             ctypes.c_int,
             [_P, _P, _P, i32, i32, _P, i32, i32, _P, _P, i32, _P, _P, i32, i32, i32] + [ctypes.c_double] * 4
             + [_P] * 15 + [sz, _P],
+        ),
+        "lg_nn_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_nn_match": (
+            ctypes.c_int,
+            [_P, _P, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double, i32] + [_P] * 9 + [sz, _P],
         ),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),

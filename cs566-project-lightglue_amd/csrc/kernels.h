@@ -477,4 +477,21 @@ struct GtDepthCall {
 size_t gt_depth_workspace_bytes(int B, int M, int N);
 hipError_t gt_matches_from_pose_depth(const GtDepthCall& c, void* workspace, hipStream_t st);
 
+// Nearest-neighbour matcher (nn_match.hip; matchers/nearest_neighbor_matcher.py:16-72).  r2 / d2: the
+// squared thresholds as the fp32 values the reference compares against; flags: 1 ratio test,
+// 2 distance test, 4 mutual check.  sim / la / num0 / num1 may be null (num0 and num1 together).
+struct NnCall {
+  const float *desc0, *desc1;  // [B][M][D], [B][N][D]
+  int B, M, N, D;
+  float r2, d2;
+  int flags;
+  const int *num0, *num1;  // per-pair counts [B]
+  float* sim;              // [B][M][N]
+  float* la;               // [B][M+1][N+1]
+  int64_t *m0, *m1;
+  float *s0, *s1;
+};
+size_t nn_workspace_bytes(int B, int M, int N, int D);
+hipError_t nn_match(const NnCall& c, void* workspace, hipStream_t st);
+
 }  // namespace lg

@@ -7,7 +7,8 @@ model registry that resolve the matcher by name.
   ``lightglue.py:666``); ``"matchers.lightglue_pretrained_MINE"`` to the wrapper below;
   ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
   HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.depth_matcher"`` to the
-  pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`).  Other components (filters,
+  pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
+  the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -181,7 +182,13 @@ def _depth_matcher():
     return DepthMatcher
 
 
-_LAZY = (_superpoint, _superglue, _homography_matcher, _depth_matcher)
+def _nn_matcher():
+    from .nn_matcher import NearestNeighborMatcher
+
+    return NearestNeighborMatcher
+
+
+_LAZY = (_superpoint, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -202,6 +209,9 @@ _REGISTRY = {
     # the pose-and-depth ground truth (matchers/depth_matcher.py), resolved lazily
     "matchers.depth_matcher": _depth_matcher,
     "depth_matcher": _depth_matcher,
+    # the nearest-neighbour baseline (matchers/nearest_neighbor_matcher.py), resolved lazily
+    "matchers.nearest_neighbor_matcher": _nn_matcher,
+    "nearest_neighbor_matcher": _nn_matcher,
 }
 
 

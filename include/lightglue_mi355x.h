@@ -267,6 +267,31 @@ int lg_gt_matches_from_pose_depth(const float* kp0, const float* kp1, const floa
                                   float* proj_1to0, uint8_t* visible0_u8, uint8_t* visible1_u8, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* Nearest-neighbour matcher: what matchers.nearest_neighbor_matcher computes
+ * (gluefactory/models/matchers/nearest_neighbor_matcher.py:16-72).  Two more entries under ABI 12.
+ * No handle.  Device inputs, fp32: desc0 [B,M,D], desc1 [B,N,D], 1 <= D <= 512 (16-byte aligned
+ * when D is a multiple of 32, 4-byte otherwise).  flags: LG_NN_RATIO / LG_NN_DISTANCE switch the two
+ * tests of find_nn on (ratio2 / dist2 are ratio_thresh^2 / distance_thresh^2 in double; they are
+ * compared as fp32, as the reference's Python floats are), LG_NN_MUTUAL the mutual check.
+ * num0 / num1 (nullable, together): device int32 [B] per-pair counts of a ragged batch; padded
+ * points never win a neighbour search, their matches are -1 and their scores 0.
+ * Device outputs: matches0 [B,M] / matches1 [B,N] int64 (-1 = none; the lowest index on exact
+ * ties), scores0 / scores1 fp32 = (match > -1); similarity [B,M,N] (nullable; 0 outside a ragged
+ * pair's real block); log_assignment [B,M+1,N+1] (nullable) = log_softmax over columns +
+ * log_softmax over rows, last row and column 0 (-inf outside a ragged pair's real block).  With
+ * both dense outputs null nothing of size M*N is written.  The products run as fp16x3 on the matrix
+ * cores (error <= 2.4e-7 sum_k |a_k b_k|).  No atomics on results, identical results run to run.
+ * Stream-ordered, asynchronous.  Workspace: lg_nn_workspace_bytes, 256-byte aligned.
+ * LG_E_INVALID: a null required pointer, a negative size, B*M*N >= 2^31, D outside [1, 512], the ratio
+ * test with M or N == 1, one of num0 / num1 alone, a short, missing or misaligned workspace, a
+ * misaligned pointer.  B, M or N == 0: LG_OK, nothing launched, no output written. */
+enum { LG_NN_RATIO = 1, LG_NN_DISTANCE = 2, LG_NN_MUTUAL = 4 };
+int lg_nn_workspace_bytes(int32_t B, int32_t M, int32_t N, int32_t D, int32_t flags, size_t* bytes);
+int lg_nn_match(const float* desc0, const float* desc1, int32_t B, int32_t M, int32_t N, int32_t D, double ratio2,
+                double dist2, int32_t flags, const int32_t* num0_or_null, const int32_t* num1_or_null,
+                float* similarity_or_null, float* log_assignment_or_null, int64_t* matches0, int64_t* matches1,
+                float* scores0, float* scores1, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
