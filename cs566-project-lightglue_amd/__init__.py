@@ -20,6 +20,10 @@ def __getattr__(name):
         from .superpoint import SuperPoint
 
         return SuperPoint
+    if name == "SuperPointOpen":
+        from .superpoint_open import SuperPoint
+
+        return SuperPoint
     if name in ("SuperGlue", "NLLLoss"):
         from . import superglue
 

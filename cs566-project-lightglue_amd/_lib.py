@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "lg_train_attention_backward",
     # SuperPoint extractor (include/superpoint_mi355x.h)
     "sp_create",
+    "sp_open_create",
     "sp_destroy",
     "sp_weight_count",
     "sp_weight_name",
@@ -184,6 +185,15 @@ class SPConfig(ctypes.Structure):  # sp_config_t
         ("refinement_radius", ctypes.c_int32),
         ("remove_borders", ctypes.c_int32),
         ("legacy_sampling", ctypes.c_int32),
+        ("detection_threshold", ctypes.c_float),
+    ]
+
+
+class SPOpenConfig(ctypes.Structure):  # sp_open_config_t
+    _fields_ = [
+        ("descriptor_dim", ctypes.c_int32),
+        ("nms_radius", ctypes.c_int32),
+        ("remove_borders", ctypes.c_int32),
         ("detection_threshold", ctypes.c_float),
     ]
 
@@ -367,6 +377,7 @@ def load():
             [_P, _P, _P, _P, _P, _P, i32, i32, i32, i32, ctypes.c_float, _P, _P, _P, _P, _P],
         ),
         "sp_create": (ctypes.c_int, [ctypes.POINTER(SPConfig), ctypes.c_int, ctypes.POINTER(_P)]),
+        "sp_open_create": (ctypes.c_int, [ctypes.POINTER(SPOpenConfig), ctypes.c_int, ctypes.POINTER(_P)]),
         "sp_destroy": (ctypes.c_int, [_P]),
         "sp_weight_count": (ctypes.c_int, [_P]),
         "sp_weight_name": (ctypes.c_char_p, [_P, ctypes.c_int]),

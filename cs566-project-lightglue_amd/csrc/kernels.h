@@ -364,8 +364,11 @@ hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M,
 // implicit GEMM reads its last row for every tap that falls outside the image.
 //
 // gray (RGB: 0.299 r + 0.587 g + 0.114 b) + conv1a (1 -> 64, 3x3, pad 1) + bias + ReLU -> planes
-hipError_t sp_conv1a(const float* image, int B, int C, int H, int W, const float* w, const float* bias, _Float16* Y,
-                     int yrows_pad, const RangeOut& ro, hipStream_t st);
+// post_scale / post_shift [64] (both or neither): y = relu(.) * s[c] + t[c], the open SuperPoint's
+// conv -> ReLU -> BatchNorm block (superpoint_open.py:57-73)
+hipError_t sp_conv1a(const float* image, int B, int C, int H, int W, const float* w, const float* bias,
+                     const float* post_scale, const float* post_shift, _Float16* Y, int yrows_pad, const RangeOut& ro,
+                     hipStream_t st);
 // 3x3 convolution (pad 1) as an implicit fp16x3 GEMM + bias + ReLU (+ 2x2 max-pool, floor):
 //   Y = planes of relu(conv(X) + bias) [B*H*W rows] or of its pool [B*(H/2)*(W/2) rows]
 struct ConvH3Args {
@@ -381,11 +384,23 @@ struct ConvH3Args {
   int x_slot;
   RangeOut ro;           // Y
   int pool;
+  // nullable (both or neither): a per-channel affine after the ReLU and before the pool,
+  //   Y = pool(relu(conv(X) + bias) * post_scale[c] + post_shift[c])
+  // (null: a separate instantiation, the code above unchanged).  ro then bounds |Y| with
+  // g0 = max|s| * rowL1, add = max|s| * max|bias| + max|t|
+  const float* post_scale;
+  const float* post_shift;
 };
 hipError_t sp_conv3x3(const ConvH3Args& a, hipStream_t st);
 hipError_t sp_zero_rows(_Float16* planes, long long ps, int rows_pad, int K, int R, hipStream_t st);
 // conv weight [Cout][Cin][k][k] -> dst [Cout][k*k*Cin] (column (k*ky + kx)*Cin + ci)
 hipError_t sp_repack_conv(const float* w, int Cout, int Cin, int ksize, float* dst, hipStream_t st);
+// eval BatchNorm -> affine: s = gamma / sqrt(var + eps), t = beta - mean * s; stats (nullable)
+// [2] = max |s|, max |t|
+hipError_t sp_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, int n, float eps,
+                      float* s, float* t, float* stats, hipStream_t st);
+// in place: W[r][:] *= s[r], bias[r] = s[r] * bias[r] + t[r]  (W [rows][K])
+hipError_t sp_scale_rows(float* W, float* bias, const float* s, const float* t, int rows, int K, hipStream_t st);
 // detector head: 65 logits per cell (row stride ld) -> softmax without the dustbin, unfolded:
 // scores[b][8y + dy][8x + dx] = p[8 dy + dx] (superpoint.py:224-230)
 hipError_t sp_detector_scores(const float* logits, int ld, int B, int Hc, int Wc, float* scores, hipStream_t st);
@@ -412,6 +427,8 @@ hipError_t sp_keypoints(const int* sel_idx, const int* n, int B, int cap, int Hs
                         int radius, float* kpts, hipStream_t st);
 // bilinear descriptor sampling at (x, y) keypoints + L2 normalisation (superpoint.py:117-149);
 // desc NHWC [B][Hc][Wc][256]; out [B][cap][256]; kpts_out (nullable) = kpts + 0.5
+// legacy: 1 / 0 = the nonfree model's two modes, 2 = the open model's grid
+// (superpoint_open.py:18-29: (k + 0.5) / (8 size), align_corners=False)
 hipError_t sp_sample(const float* kpts, const int* n, int B, int cap, const float* desc, int Hc, int Wc, int legacy,
                      float* out, float* kpts_out, hipStream_t st);
 

@@ -15,6 +15,12 @@
 // order (the four pixels of a pooling window are consecutive GEMM rows = the four accumulator
 // registers of one lane of a 16x16 MFMA tile): the pool is a max over one lane's registers and
 // only the pooled map is written.
+//
+// The open SuperPoint (gluefactory/models/extractors/superpoint_open.py) runs through the same
+// kernels: its blocks are conv -> ReLU -> BatchNorm with the pool after the BatchNorm, which the AFF
+// variants of the convolution kernels apply as a per-channel affine after the ReLU (the pool then
+// takes the window's minimum where the scale is negative); sp_bn_fold / sp_scale_rows fold the
+// BatchNorms at load time, sp_sample has its grid as a third mode.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -46,11 +52,17 @@ unsigned grid_for(long long n, int block, int cap = 8192) {
 // (zero padded) in registers -> ReLU -> fp16x3 planes.  A wave's store covers 16 consecutive
 // 64-byte rows = 1 KiB contiguous (one thread per pixel with 16-byte stores at a 64-byte stride
 // wrote each line in four partial pieces and ran at half the store rate).
+// AFF (the open SuperPoint's VGGBlock, superpoint_open.py:57-73): a per-channel affine after the
+// ReLU, y = relu(.) * s[c] + t[c] -- the eval BatchNorm folded to (s, t) at load time.
+template <bool AFF>
 __global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* __restrict__ img, int B, int C, int H, int W,
                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                        const float* __restrict__ ps, const float* __restrict__ pt,
                                                         _Float16* Y, int yrows_pad, RangeOut ro) {
-  __shared__ float wsh[64 * 9 + 64];
+  __shared__ float wsh[64 * 9 + 64 + (AFF ? 128 : 0)];
   for (int i = threadIdx.x; i < 64 * 9 + 64; i += blockDim.x) wsh[i] = i < 64 * 9 ? w[i] : bias[i - 64 * 9];
+  if constexpr (AFF)
+    for (int i = threadIdx.x; i < 128; i += blockDim.x) wsh[64 * 9 + 64 + i] = i < 64 ? ps[i] : pt[i - 64];
   __syncthreads();
   const int eo = range_exponent(ro);
   const float so = ldexpf(1.f, -eo);
@@ -88,8 +100,13 @@ __global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* __restrict_
         float a = 0.f;
 #pragma unroll
         for (int k = 0; k < 9; ++k) a = fmaf(wsh[co * 9 + k], g[k], a);
-        const float v = fmaxf(a + wsh[64 * 9 + co], 0.f);
-        wmax = fmaxf(wmax, v);
+        float v = fmaxf(a + wsh[64 * 9 + co], 0.f);
+        if constexpr (AFF) {
+          v = fmaf(v, wsh[64 * 9 + 64 + co], wsh[64 * 9 + 128 + co]);
+          wmax = fmaxf(wmax, fabsf(v));
+        } else {
+          wmax = fmaxf(wmax, v);
+        }
         _Float16 hh, ll;
         split2h(v * so, hh, ll);
         h[e] = hh;
@@ -103,12 +120,19 @@ __global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* __restrict_
   range_commit(ro, wmax, eo);
 }
 
-hipError_t sp_conv1a(const float* image, int B, int C, int H, int W, const float* w, const float* bias, _Float16* Y,
-                     int yrows_pad, const RangeOut& ro, hipStream_t st) {
+hipError_t sp_conv1a(const float* image, int B, int C, int H, int W, const float* w, const float* bias,
+                     const float* post_scale, const float* post_shift, _Float16* Y, int yrows_pad, const RangeOut& ro,
+                     hipStream_t st) {
   if (B <= 0 || H <= 0 || W <= 0) return hipSuccess;
   if ((C != 1 && C != 3) || (long long)yrows_pad < (long long)B * H * W) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sp_conv1a_kernel, dim3(grid_for(4LL * B * H * W, 256, 8192)), dim3(256), 0, st, image, B, C,
-                     H, W, w, bias, Y, yrows_pad, ro);
+  if (!post_scale != !post_shift) return hipErrorInvalidValue;
+  const dim3 grid(grid_for(4LL * B * H * W, 256, 8192));
+  if (post_scale)
+    hipLaunchKernelGGL(sp_conv1a_kernel<true>, grid, dim3(256), 0, st, image, B, C, H, W, w, bias, post_scale, post_shift, Y,
+                       yrows_pad, ro);
+  else
+    hipLaunchKernelGGL(sp_conv1a_kernel<false>, grid, dim3(256), 0, st, image, B, C, H, W, w, bias, post_scale, post_shift,
+                       Y, yrows_pad, ro);
   return hipGetLastError();
 }
 
@@ -117,7 +141,8 @@ hipError_t sp_conv1a(const float* image, int B, int C, int H, int W, const float
 // per product as in gemm_h3.hip), NSTAGE LDS stages.  k-tile kt = (tap, 32-channel block).
 // BN = 128 (8 waves, 2 per SIMD, no spills) for Cout % 128 == 0, else 64; a 256-wide tile would
 // need 16 waves at 128 VGPRs and spills its gather state.
-template <int BN, int NSTAGE, bool POOL>
+// AFF: the post-ReLU affine of the open SuperPoint (ConvH3Args::post_scale / post_shift).
+template <int BN, int NSTAGE, bool POOL, bool AFF>
 __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Args g) {
   constexpr int BM = 256, BK = kKB;
   constexpr int WGN = BN / 64, NW = 4 * WGN;
@@ -229,12 +254,24 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
   const f32x4 b1 = *reinterpret_cast<const f32x4*>(g.bias + col0 + 4);
   const float so = ldexpf(1.f, -eo);
   float wmax = 0.f;
+  // AFF: bias, ReLU and the affine are applied before the transpose, where a lane holds one
+  // channel (c = j 16 + (lane & 15)); store8 then only splits (as in the halo kernel below)
+  struct Aff {
+    float b, s, t;
+  };
+  auto aff_load = [&](int ch) { return Aff{g.bias[ch], g.post_scale[ch], g.post_shift[ch]}; };
+  auto aff_tail = [&](float a, const Aff& f) { return fmaf(fmaxf(fmaf(a, accs, f.b), 0.f), f.s, f.t); };
   auto store8 = [&](int row, f32x4 v0, f32x4 v1) {
     f16x8 h, l;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float v = fmaxf(fmaf(e < 4 ? v0[e] : v1[e - 4], accs, e < 4 ? b0[e] : b1[e - 4]), 0.f);
-      wmax = fmaxf(wmax, v);
+      float v = e < 4 ? v0[e] : v1[e - 4];
+      if constexpr (AFF) {
+        wmax = fmaxf(wmax, fabsf(v));
+      } else {
+        v = fmaxf(fmaf(v, accs, e < 4 ? b0[e] : b1[e - 4]), 0.f);
+        wmax = fmaxf(wmax, v);
+      }
       _Float16 a, c;
       split2h(v * so, a, c);
       h[e] = a;
@@ -250,12 +287,16 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
+          Aff f{};
+          if constexpr (AFF) f = aff_load(n0 + wn0 + j * 16 + (lane & 15));
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int rr = a * 16 + (lane >> 4) * 4 + r, c = j * 16 + (lane & 15);
-            ep[rr * 64 + (c ^ ((rr & 1) << 2))] = acc[2 * i + a][j][r];
+            if constexpr (AFF) ep[rr * 64 + (c ^ ((rr & 1) << 2))] = aff_tail(acc[2 * i + a][j][r], f);
+            else ep[rr * 64 + (c ^ ((rr & 1) << 2))] = acc[2 * i + a][j][r];
           }
+        }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -275,7 +316,15 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64) void sp_conv3x3_kernel(ConvH3Ar
         for (int j = 0; j < 4; ++j) {
           const f32x4 v = acc[2 * i + a][j];
           const int pr_ = a * 4 + (lane >> 4), c = j * 16 + (lane & 15);
-          ep[pr_ * 64 + (c ^ ((pr_ & 1) << 2))] = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+          float pv = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+          // AFF: the pool follows the affine; the tail is monotone in the accumulator, decreasing
+          // for s < 0, where the window's maximum is the tail of its SMALLEST accumulator
+          if constexpr (AFF) {
+            const Aff f = aff_load(n0 + wn0 + c);
+            if (f.s < 0.f) pv = fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
+            pv = aff_tail(pv, f);
+          }
+          ep[pr_ * 64 + (c ^ ((pr_ & 1) << 2))] = pv;
         }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const int rr = lane >> 3;
@@ -340,7 +389,7 @@ __device__ __forceinline__ bool halo_inv(int lr, int s, int& y, int& x, int& c) 
   c = 2 * (((s >> 1) ^ x) & 1) + (s & 1);
   return true;
 }
-template <int BN, bool POOL>
+template <int BN, bool POOL, bool AFF>
 __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(ConvH3Args g) {
   constexpr int BK = kKB, WGN = BN / 64, NW = 8 * WGN, WM = 32, WMT = WM / 16;
   constexpr int HALO_PLANE = kHRows * BK * 2, HALO_BYTES = 2 * HALO_PLANE;
@@ -456,22 +505,43 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
   const float so = ldexpf(1.f, -eo);
   float wmax = 0.f;
   auto store8 = [&](int row, int col0, f32x4 v0, f32x4 v1) {
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(g.bias + col0);
-    const f32x4 b1 = *reinterpret_cast<const f32x4*>(g.bias + col0 + 4);
     f16x8 h, l;
+    if constexpr (AFF) {  // finished values (aff_tail below): only the split is left
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = fmaxf(fmaf(e < 4 ? v0[e] : v1[e - 4], accs, e < 4 ? b0[e] : b1[e - 4]), 0.f);
-      wmax = fmaxf(wmax, v);
-      _Float16 a, c;
-      split2h(v * so, a, c);
-      h[e] = a;
-      l[e] = c;
+      for (int e = 0; e < 8; ++e) {
+        const float v = e < 4 ? v0[e] : v1[e - 4];
+        wmax = fmaxf(wmax, fabsf(v));
+        _Float16 a, c;
+        split2h(v * so, a, c);
+        h[e] = a;
+        l[e] = c;
+      }
+    } else {
+      const f32x4 b0 = *reinterpret_cast<const f32x4*>(g.bias + col0);
+      const f32x4 b1 = *reinterpret_cast<const f32x4*>(g.bias + col0 + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float v = fmaxf(fmaf(e < 4 ? v0[e] : v1[e - 4], accs, e < 4 ? b0[e] : b1[e - 4]), 0.f);
+        wmax = fmaxf(wmax, v);
+        _Float16 a, c;
+        split2h(v * so, a, c);
+        h[e] = a;
+        l[e] = c;
+      }
     }
     const size_t off = plane_off(row, col0, g.yrows_pad);
     *reinterpret_cast<f16x8*>(g.Y + off) = h;
     *reinterpret_cast<f16x8*>(g.Y + g.yps + off) = l;
   };
+  // AFF: bias, ReLU and the affine are applied BEFORE the transpose, where a lane holds one
+  // channel (c = j 16 + (lane & 15)) in its four accumulator registers: three scalars per lane
+  // and j, loaded in the epilogue (nothing is held across the k-loop: the BN = 128 form runs
+  // 1024 threads at a 128-VGPR budget), and no vector of b / s / t in store8
+  struct Aff {
+    float b, s, t;
+  };
+  auto aff_load = [&](int ch) { return Aff{g.bias[ch], g.post_scale[ch], g.post_shift[ch]}; };
+  auto aff_tail = [&](float a, const Aff& f) { return fmaf(fmaxf(fmaf(a, accs, f.b), 0.f), f.s, f.t); };
 
   // prologue: halo 0, weights of steps 0 and 1
   Tile cur = decode(0);
@@ -520,12 +590,16 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
         for (int h = 0; h < 16 / EPR; ++h) {
           if ((lane >> 4) / (EPR / 4) == h)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j) {
+              Aff f{};
+              if constexpr (AFF) f = aff_load(cur.n0 + wn0 + j * 16 + (lane & 15));
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int rr = ((lane >> 4) % (EPR / 4)) * 4 + r, c = j * 16 + (lane & 15);
-                ep[rr * 64 + (c ^ ((rr & 1) << 2))] = acc[a][j][r];
+                if constexpr (AFF) ep[rr * 64 + (c ^ ((rr & 1) << 2))] = aff_tail(acc[a][j][r], f);
+                else ep[rr * 64 + (c ^ ((rr & 1) << 2))] = acc[a][j][r];
               }
+            }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
           for (int kk = 0; kk < EPR / 8; ++kk) {
@@ -550,7 +624,17 @@ __global__ __launch_bounds__(8 * (BN / 64) * 64) void sp_conv3x3_halo_kernel(Con
           for (int j = 0; j < 4; ++j) {
             const f32x4 v = acc[a2 * 4 + a][j];
             const int pr_ = a * 4 + (lane >> 4), c = j * 16 + (lane & 15);
-            ep[pr_ * 64 + (c ^ ((pr_ & 1) << 2))] = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+            float pv = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+            // AFF: the pool follows the affine.  relu(. + b) s + t is monotone in the accumulator,
+            // increasing for s > 0 and decreasing for s < 0 (rounding is monotone too), so the
+            // window's maximum is the tail of its largest accumulator for s >= 0 and of its
+            // SMALLEST for s < 0 (s == 0: either gives t)
+            if constexpr (AFF) {
+              const Aff f = aff_load(cur.n0 + wn0 + c);
+              if (f.s < 0.f) pv = fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
+              pv = aff_tail(pv, f);
+            }
+            ep[pr_ * 64 + (c ^ ((pr_ & 1) << 2))] = pv;
           }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -586,14 +670,20 @@ template <int BN, bool POOL>
 static hipError_t sp_conv3x3_halo_launch(const ConvH3Args& a, hipStream_t st) {
   const int tiles = a.B * ((a.H + kHT - 1) / kHT) * ((a.W + kHT - 1) / kHT) * (a.Cout / BN);
   const int grid = std::min(tiles, sp_num_cus());  // one workgroup per CU (LDS-limited)
-  hipLaunchKernelGGL((sp_conv3x3_halo_kernel<BN, POOL>), dim3(grid), dim3(8 * (BN / 64) * 64), 0, st, a);
+  if (a.post_scale)
+    hipLaunchKernelGGL((sp_conv3x3_halo_kernel<BN, POOL, true>), dim3(grid), dim3(8 * (BN / 64) * 64), 0, st, a);
+  else
+    hipLaunchKernelGGL((sp_conv3x3_halo_kernel<BN, POOL, false>), dim3(grid), dim3(8 * (BN / 64) * 64), 0, st, a);
   return hipGetLastError();
 }
 
 template <int BN, int NS, bool POOL>
 static hipError_t sp_conv3x3_launch(const ConvH3Args& a, int R, hipStream_t st) {
   const int tiles = ((R + 255) / 256) * (a.Cout / BN);
-  hipLaunchKernelGGL((sp_conv3x3_kernel<BN, NS, POOL>), dim3(tiles), dim3(4 * (BN / 64) * 64), 0, st, a);
+  if (a.post_scale)
+    hipLaunchKernelGGL((sp_conv3x3_kernel<BN, NS, POOL, true>), dim3(tiles), dim3(4 * (BN / 64) * 64), 0, st, a);
+  else
+    hipLaunchKernelGGL((sp_conv3x3_kernel<BN, NS, POOL, false>), dim3(tiles), dim3(4 * (BN / 64) * 64), 0, st, a);
   return hipGetLastError();
 }
 
@@ -604,6 +694,7 @@ hipError_t sp_conv3x3(const ConvH3Args& a, hipStream_t st) {
   if (a.Cin % kKB || a.Cout % 64 || !a.X.p || !a.Wt.p || !a.Y || !a.bias || a.X.rows_pad <= rin || a.X.rows_pad % 256 ||
       a.Wt.rows_pad != a.Cout || a.yrows_pad < rout || a.X.rows_pad > (1 << 26))  // 32-bit DMA byte offsets
     return hipErrorInvalidValue;
+  if (!a.post_scale != !a.post_shift) return hipErrorInvalidValue;
   if (a.pool && (a.H < 2 || a.W < 2)) return hipErrorInvalidValue;
   const char* conv = getenv("LG_SP_CONV");  // read per launch (tests flip it between calls)
   const bool gather = conv && !strcmp(conv, "gather");
@@ -649,6 +740,60 @@ __global__ void sp_repack_kernel(const float* w, int Cout, int Cin, int k, float
 hipError_t sp_repack_conv(const float* w, int Cout, int Cin, int ksize, float* dst, hipStream_t st) {
   hipLaunchKernelGGL(sp_repack_kernel, dim3(grid_for((long long)Cout * Cin * ksize * ksize, 256, 1024)), dim3(256), 0, st, w,
                      Cout, Cin, ksize, dst);
+  return hipGetLastError();
+}
+
+// ---- eval BatchNorm as a per-channel affine (superpoint_open.py:64, running statistics) -------
+// s = gamma / sqrt(var + eps), t = beta - mean s (formed in double, rounded once);
+// stats[0] = max |s|, stats[1] = max |t|: the range bounds of the affine epilogues.  One workgroup.
+__global__ __launch_bounds__(256) void sp_bn_fold_kernel(const float* gamma, const float* beta, const float* mean,
+                                                         const float* var, int n, float eps, float* s, float* t,
+                                                         float* stats) {
+  __shared__ float red[2][4];
+  float smax = 0.f, tmax = 0.f;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const float sv = (float)((double)gamma[i] / sqrt((double)var[i] + (double)eps));
+    const float tv = (float)((double)beta[i] - (double)mean[i] * (double)sv);
+    s[i] = sv;
+    t[i] = tv;
+    smax = fmaxf(smax, fabsf(sv));
+    tmax = fmaxf(tmax, fabsf(tv));
+  }
+  smax = wave_max_dpp(smax);
+  tmax = wave_max_dpp(tmax);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = smax;
+    red[1][threadIdx.x >> 6] = tmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && stats) {
+    stats[0] = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    stats[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  }
+}
+
+hipError_t sp_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, int n, float eps,
+                      float* s, float* t, float* stats, hipStream_t st) {
+  if (n <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sp_bn_fold_kernel, dim3(1), dim3(256), 0, st, gamma, beta, mean, var, n, eps, s, t, stats);
+  return hipGetLastError();
+}
+
+// A BatchNorm that follows its convolution directly (no ReLU between: the 1x1 heads) folds into
+// it: W'[r][:] = s[r] W[r][:], b'[r] = s[r] b[r] + t[r].
+__global__ void sp_scale_rows_kernel(float* W, float* bias, const float* s, const float* t, int rows, int K) {
+  const long long total = (long long)rows * K;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / K);
+    W[i] = mul_rn(W[i], s[r]);
+    if (i - (long long)r * K == 0) bias[r] = fmaf(s[r], bias[r], t[r]);
+  }
+}
+
+hipError_t sp_scale_rows(float* W, float* bias, const float* s, const float* t, int rows, int K, hipStream_t st) {
+  if (rows <= 0 || K <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sp_scale_rows_kernel, dim3(grid_for((long long)rows * K, 256, 1024)), dim3(256), 0, st, W, bias, s, t,
+                     rows, K);
   return hipGetLastError();
 }
 
@@ -1032,6 +1177,7 @@ hipError_t sp_keypoints(const int* sel_idx, const int* n, int B, int cap, int Hs
 // grid_sample(bilinear, zero padding) in torch's CPU formulation: normalised grid g = 2 k' - 1,
 // unnormalised with align_corners=True (legacy) as (g + 1) * ((W - 1) / 2), else
 // (g + 1) * (W / 2) - 0.5; then F.normalize over the channels.  One wave per keypoint.
+// legacy: 1 = superpoint.py:117-133, 0 = :138-149, 2 = the open model's (superpoint_open.py:18-29).
 __global__ void sp_sample_kernel(const float* kpts, const int* n, int B, int cap, const float* desc, int Hc, int Wc,
                                  int legacy, float* out, float* kout) {
   const int lane = threadIdx.x & 63;
@@ -1041,7 +1187,7 @@ __global__ void sp_sample_kernel(const float* kpts, const int* n, int B, int cap
     if (i >= n[b]) continue;
     const float x = kpts[2 * w], y = kpts[2 * w + 1];
     float gx, gy, ix, iy;
-    if (legacy) {  // k - s/2 + 0.5, / (size*s - s/2 - 0.5), *2 - 1
+    if (legacy == 1) {  // k - s/2 + 0.5, / (size*s - s/2 - 0.5), *2 - 1
       gx = div_rn(add_rn(sub_rn(x, 4.f), 0.5f), (float)(Wc * 8) - 4.5f);
       gy = div_rn(add_rn(sub_rn(y, 4.f), 0.5f), (float)(Hc * 8) - 4.5f);
       gx = sub_rn(mul_rn(gx, 2.f), 1.f);
@@ -1049,8 +1195,10 @@ __global__ void sp_sample_kernel(const float* kpts, const int* n, int B, int cap
       ix = mul_rn(add_rn(gx, 1.f), (float)(Wc - 1) * 0.5f);
       iy = mul_rn(add_rn(gy, 1.f), (float)(Hc - 1) * 0.5f);
     } else {
-      gx = sub_rn(mul_rn(div_rn(x, (float)(Wc * 8)), 2.f), 1.f);
-      gy = sub_rn(mul_rn(div_rn(y, (float)(Hc * 8)), 2.f), 1.f);
+      // legacy == 2 (superpoint_open.py:18-29): the pixel centre, (k + 0.5) / (8 size)
+      const float cx = legacy == 2 ? add_rn(x, 0.5f) : x, cy = legacy == 2 ? add_rn(y, 0.5f) : y;
+      gx = sub_rn(mul_rn(div_rn(cx, (float)(Wc * 8)), 2.f), 1.f);
+      gy = sub_rn(mul_rn(div_rn(cy, (float)(Hc * 8)), 2.f), 1.f);
       ix = sub_rn(mul_rn(add_rn(gx, 1.f), (float)Wc * 0.5f), 0.5f);
       iy = sub_rn(mul_rn(add_rn(gy, 1.f), (float)Hc * 0.5f), 0.5f);
     }

@@ -1,5 +1,7 @@
 // C-ABI of the SuperPoint extractor (include/superpoint_mi355x.h): handle, weight repacking and
-// the eval forward orchestration (reference gluefactory_nonfree/superpoint.py:202-350).
+// the eval forward orchestration (reference gluefactory_nonfree/superpoint.py:202-350), for both
+// architectures: the nonfree model (sp_create) and the open one (sp_open_create, reference
+// gluefactory/models/extractors/superpoint_open.py:76-207), which share the handle type.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +62,32 @@ std::vector<Tensor> make_schema(const sp_config_t& c) {
   return s;
 }
 
+// The twelve convolutions by role (0-7 encoder, 8/9 detector head, 10/11 descriptor head) under
+// their module names in the two models
+constexpr int kArchNonfree = 0, kArchOpen = 1;
+const char* const kNonfreeNames[12] = {"conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b",
+                                       "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb"};
+const char* const kOpenNames[12] = {"backbone.0.0", "backbone.0.1", "backbone.1.0", "backbone.1.1",
+                                    "backbone.2.0", "backbone.2.1", "backbone.3.0", "backbone.3.1",
+                                    "detector.0",   "detector.1",   "descriptor.0", "descriptor.1"};
+constexpr float kOpenBnEps = 1e-3f;  // superpoint_open.py:64
+
+// superpoint_open.py:91-112, registration order (lightglue_amd.sp_weights.superpoint_open_schema);
+// bn.num_batches_tracked (int64) is not part of the fp32 interface
+std::vector<Tensor> make_open_schema(int descriptor_dim) {
+  const int ci[12] = {1, 64, 64, 64, 64, 128, 128, 128, 128, 256, 128, 256};
+  const int co[12] = {64, 64, 64, 64, 128, 128, 128, 128, 256, 65, 256, descriptor_dim};
+  std::vector<Tensor> s;
+  for (int i = 0; i < 12; ++i) {
+    const std::string n = kOpenNames[i];
+    const int k = (i == 9 || i == 11) ? 1 : 3;
+    s.push_back({n + ".conv.weight", {co[i], ci[i], k, k}});
+    s.push_back({n + ".conv.bias", {co[i]}});
+    for (const char* b : {"weight", "bias", "running_mean", "running_var"}) s.push_back({n + ".bn." + b, {co[i]}});
+  }
+  return s;
+}
+
 constexpr int kSlots = 16;
 size_t a256(size_t n) { return (n + 255) & ~size_t(255); }
 int rows_pad_for(long long R) { return (int)(((R + 1) + 255) / 256 * 256); }  // >= R + 1: a zero row
@@ -72,6 +100,9 @@ struct Mat {
   float unscale = 1.f;
   size_t boff = 0;   // bias (floats into gbuf)
   float g = 0.f, bmax = 0.f;
+  // open model: the block's BatchNorm as an affine after the ReLU (floats into gbuf), max |s|, max |t|
+  size_t soff = 0, toff = 0;
+  float smax = 1.f, tmax = 0.f;
 };
 
 struct Shape {
@@ -147,6 +178,10 @@ struct sp_handle {
   Mat enc[7];                // conv1b .. conv4b
   Mat heads, pb, db;         // [convPa | convDa], convPb (rows padded to 256), convDb
   float g1a = 0.f, b1a = 0.f;
+  int arch = kArchNonfree;   // selects the schema, the affine epilogues and the sampling mode
+  int sample_mode = 0;       // lg::sp_sample's `legacy`
+  size_t s1a = 0, t1a = 0;   // open: conv1a's affine (floats into gbuf)
+  float smax1a = 1.f, tmax1a = 0.f;
   bool loaded = false;
   Shape last{};
   bool have_last = false;
@@ -157,10 +192,7 @@ static int layer_index(const sp_handle* h, const std::string& name) {
   return it == h->index.end() ? -1 : it->second;
 }
 
-extern "C" {
-
-int sp_create(const sp_config_t* cfg, int device, sp_handle_t** out) {
-  if (!cfg || !out) return fail(LG_E_INVALID, "null argument");
+static int create_handle(const sp_config_t* cfg, int arch, int device, sp_handle_t** out) {
   if (cfg->descriptor_dim != 256) return fail(LG_E_INVALID, "descriptor_dim must be 256");
   if (cfg->nms_radius < 0 || cfg->nms_radius > 8) return fail(LG_E_INVALID, "nms_radius must be in [0, 8]");
   if (cfg->refinement_radius < 0 || cfg->remove_borders < 0) return fail(LG_E_INVALID, "negative radius / border");
@@ -171,7 +203,9 @@ int sp_create(const sp_config_t* cfg, int device, sp_handle_t** out) {
   auto* h = new sp_handle();
   h->cfg = *cfg;
   h->device = device;
-  h->schema = make_schema(*cfg);
+  h->arch = arch;
+  h->sample_mode = arch == kArchOpen ? 2 : (cfg->legacy_sampling ? 1 : 0);
+  h->schema = arch == kArchOpen ? make_open_schema(cfg->descriptor_dim) : make_schema(*cfg);
   size_t off = 0;
   for (size_t i = 0; i < h->schema.size(); ++i) {
     h->index[h->schema[i].name] = (int)i;
@@ -185,6 +219,20 @@ int sp_create(const sp_config_t* cfg, int device, sp_handle_t** out) {
   }
   *out = h;
   return LG_OK;
+}
+
+extern "C" {
+
+int sp_create(const sp_config_t* cfg, int device, sp_handle_t** out) {
+  if (!cfg || !out) return fail(LG_E_INVALID, "null argument");
+  return create_handle(cfg, kArchNonfree, device, out);
+}
+
+int sp_open_create(const sp_open_config_t* cfg, int device, sp_handle_t** out) {
+  if (!cfg || !out) return fail(LG_E_INVALID, "null argument");
+  // detector and descriptor always; no refinement; the sampling mode follows the architecture tag
+  const sp_config_t c{1, 1, cfg->descriptor_dim, cfg->nms_radius, 0, cfg->remove_borders, 0, cfg->detection_threshold};
+  return create_handle(&c, kArchOpen, device, out);
 }
 
 int sp_destroy(sp_handle_t* h) {
@@ -224,11 +272,18 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   for (int i = 0; i < n; ++i)
     SP_HIP(hipMemcpyAsync(h->wbuf + h->woff[layer_index(h, names[i])], tensors[i], numels[i] * sizeof(float),
                           hipMemcpyDeviceToDevice, st));
-  auto W = [&](const char* nm) { return h->wbuf + h->woff[layer_index(h, std::string(nm) + ".weight")]; };
-  auto Bi = [&](const char* nm) { return h->wbuf + h->woff[layer_index(h, std::string(nm) + ".bias")]; };
+  const bool open = h->arch == kArchOpen;
+  auto T = [&](const std::string& nm) { return h->wbuf + h->woff[layer_index(h, nm)]; };
+  auto W = [&](int role) { return T(open ? std::string(kOpenNames[role]) + ".conv.weight" : std::string(kNonfreeNames[role]) + ".weight"); };
+  auto Bi = [&](int role) { return T(open ? std::string(kOpenNames[role]) + ".conv.bias" : std::string(kNonfreeNames[role]) + ".bias"); };
+  // open: the role's BatchNorm -> (s, t) [n] and stats (max |s|, max |t|, nullable)
+  auto fold = [&](int role, int n, float* s, float* t, float* stats) {
+    const std::string b = std::string(kOpenNames[role]) + ".bn.";
+    return lg::sp_bn_fold(T(b + "weight"), T(b + "bias"), T(b + "running_mean"), T(b + "running_var"), n, kOpenBnEps, s, t,
+                          stats, st);
+  };
 
   // repacked GEMM matrices: [Cout][9 Cin] for 3x3 (k = (3 ky + kx) Cin + ci), [Cout][Cin] for 1x1
-  const char* encn[7] = {"conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b"};
   const int enc_ci[7] = {64, 64, 64, 64, 128, 128, 128}, enc_co[7] = {64, 64, 64, 128, 128, 128, 128};
   const bool det = h->cfg.has_detector, des = h->cfg.has_descriptor;
   const int Nh = 256 * ((det ? 1 : 0) + (des ? 1 : 0));
@@ -240,11 +295,21 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
     off += (size_t)rows * K;
     m.boff = off;
     off += rows;
+    if (open) {
+      m.soff = off;
+      m.toff = off + rows;
+      off += 2 * (size_t)rows;
+    }
   };
   for (int i = 0; i < 7; ++i) place(h->enc[i], enc_co[i], 9 * enc_ci[i]);
   if (Nh) place(h->heads, Nh, 9 * 128);
   if (det) place(h->pb, 256, 256);
   if (des) place(h->db, 256, 256);
+  if (open) {  // conv1a's affine
+    h->s1a = off;
+    h->t1a = off + 64;
+    off += 128;
+  }
   (void)hipFree(h->gbuf);
   (void)hipFree(h->planes);
   h->gbuf = nullptr;
@@ -253,22 +318,22 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   SP_HIP(hipMemsetAsync(h->gbuf, 0, off * sizeof(float), st));
   float* G = h->gbuf;
   for (int i = 0; i < 7; ++i) {
-    SP_HIP(lg::sp_repack_conv(W(encn[i]), enc_co[i], enc_ci[i], 3, G + h->enc[i].off, st));
-    SP_HIP(hipMemcpyAsync(G + h->enc[i].boff, Bi(encn[i]), enc_co[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(lg::sp_repack_conv(W(1 + i), enc_co[i], enc_ci[i], 3, G + h->enc[i].off, st));
+    SP_HIP(hipMemcpyAsync(G + h->enc[i].boff, Bi(1 + i), enc_co[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   int hr = 0;
   if (det) {
-    SP_HIP(lg::sp_repack_conv(W("convPa"), 256, 128, 3, G + h->heads.off, st));
-    SP_HIP(hipMemcpyAsync(G + h->heads.boff, Bi("convPa"), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(lg::sp_repack_conv(W(8), 256, 128, 3, G + h->heads.off, st));
+    SP_HIP(hipMemcpyAsync(G + h->heads.boff, Bi(8), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
     hr = 256;
-    SP_HIP(hipMemcpyAsync(G + h->pb.off, W("convPb"), 65 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->pb.boff, Bi("convPb"), 65 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(hipMemcpyAsync(G + h->pb.off, W(9), 65 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(hipMemcpyAsync(G + h->pb.boff, Bi(9), 65 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   if (des) {
-    SP_HIP(lg::sp_repack_conv(W("convDa"), 256, 128, 3, G + h->heads.off + (size_t)hr * 9 * 128, st));
-    SP_HIP(hipMemcpyAsync(G + h->heads.boff + hr, Bi("convDa"), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->db.off, W("convDb"), 256 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->db.boff, Bi("convDb"), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(lg::sp_repack_conv(W(10), 256, 128, 3, G + h->heads.off + (size_t)hr * 9 * 128, st));
+    SP_HIP(hipMemcpyAsync(G + h->heads.boff + hr, Bi(10), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(hipMemcpyAsync(G + h->db.off, W(11), 256 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SP_HIP(hipMemcpyAsync(G + h->db.boff, Bi(11), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   std::vector<Mat*> mats;
   for (auto& m : h->enc) mats.push_back(&m);
@@ -277,16 +342,29 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   if (des) mats.push_back(&h->db);
   // per matrix: absmax (plane scale 2^sw, max |W 2^sw| in [8, 16)), max row L1 and max |bias|
   // (range bounds, kernels.h RangeOut); conv1a: row L1 / bias max of its [64][9] weight
-  const int nf = (int)mats.size() * 3 + 2;
+  // open: + (max |s|, max |t|) of conv1a, conv1b .. conv4b, detector.0, descriptor.0
+  const int nf = (int)mats.size() * 3 + 2, na = open ? 20 : 0;
   float* dst = nullptr;
-  SP_HIP(hipMallocAsync((void**)&dst, nf * sizeof(float), st));
+  SP_HIP(hipMallocAsync((void**)&dst, (nf + na) * sizeof(float), st));
+  if (open) {
+    SP_HIP(fold(0, 64, G + h->s1a, G + h->t1a, dst + nf));
+    for (int i = 0; i < 7; ++i) SP_HIP(fold(1 + i, enc_co[i], G + h->enc[i].soff, G + h->enc[i].toff, dst + nf + 2 + 2 * i));
+    SP_HIP(fold(8, 256, G + h->heads.soff, G + h->heads.toff, dst + nf + 16));
+    SP_HIP(fold(10, 256, G + h->heads.soff + 256, G + h->heads.toff + 256, dst + nf + 18));
+    // the 1x1 heads have no ReLU: their BatchNorm folds into the weight rows and the bias before
+    // the statistics and the fp16x3 split below (their own s / t slots hold the folded affine)
+    SP_HIP(fold(9, 65, G + h->pb.soff, G + h->pb.toff, nullptr));
+    SP_HIP(lg::sp_scale_rows(G + h->pb.off, G + h->pb.boff, G + h->pb.soff, G + h->pb.toff, 65, 256, st));
+    SP_HIP(fold(11, 256, G + h->db.soff, G + h->db.toff, nullptr));
+    SP_HIP(lg::sp_scale_rows(G + h->db.off, G + h->db.boff, G + h->db.soff, G + h->db.toff, 256, 256, st));
+  }
   for (size_t i = 0; i < mats.size(); ++i) {
     SP_HIP(lg::absmax(G + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
     SP_HIP(lg::weight_range_stats(G + mats[i]->off, mats[i]->rows, mats[i]->K, G + mats[i]->boff, dst + 3 * i + 1, st));
   }
-  SP_HIP(lg::weight_range_stats(W("conv1a"), 64, 9, Bi("conv1a"), dst + nf - 2, st));
-  std::vector<float> hs(nf);
-  SP_HIP(hipMemcpyAsync(hs.data(), dst, nf * sizeof(float), hipMemcpyDeviceToHost, st));
+  SP_HIP(lg::weight_range_stats(W(0), 64, 9, Bi(0), dst + nf - 2, st));
+  std::vector<float> hs(nf + na);
+  SP_HIP(hipMemcpyAsync(hs.data(), dst, (nf + na) * sizeof(float), hipMemcpyDeviceToHost, st));
   SP_HIP(hipStreamSynchronize(st));
   SP_HIP(hipFreeAsync(dst, st));
   size_t ptotal = 0;
@@ -310,6 +388,16 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   }
   h->g1a = hs[nf - 2];
   h->b1a = hs[nf - 1];
+  if (open) {
+    h->smax1a = hs[nf];
+    h->tmax1a = hs[nf + 1];
+    for (int i = 0; i < 7; ++i) {
+      h->enc[i].smax = hs[nf + 2 + 2 * i];
+      h->enc[i].tmax = hs[nf + 3 + 2 * i];
+    }
+    h->heads.smax = std::max(hs[nf + 16], hs[nf + 18]);
+    h->heads.tmax = std::max(hs[nf + 17], hs[nf + 19]);
+  }
   h->loaded = true;
   return LG_OK;
 }
@@ -330,6 +418,10 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
   const Shape s = make_shape(in->B, in->C, in->H, in->W, out->capacity);
   if (s.Hc < 1 || s.Wc < 1) return fail(LG_E_INVALID, "image smaller than 8 x 8");
   const bool sparse = in->sparse != 0;
+  const bool open = h->arch == kArchOpen;
+  if (open && !sparse) return fail(LG_E_INVALID, "the open SuperPoint has no dense-only mode (sparse must be 1)");
+  if (open && in->image_size)
+    return fail(LG_E_INVALID, "the open SuperPoint removes borders at the map's edges: image_size must be NULL");
   if (sparse && !(c.has_detector && c.has_descriptor))
     return fail(LG_E_INVALID, "sparse outputs need the detector and the descriptor (superpoint.py:239)");
   if (sparse && (!out->keypoints || !out->keypoint_scores || !out->counts))
@@ -355,10 +447,15 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
     return lg::RangeOut{w.rtab, in_slot, -1, g, 0.f, add, out_slot, 1};
   };
   // gray weights sum to 1: |gray| <= max |image|
-  const float* W1a = h->wbuf + h->woff[layer_index(h, "conv1a.weight")];
-  const float* B1a = h->wbuf + h->woff[layer_index(h, "conv1a.bias")];
   const int rp1 = rows_pad_for(s.R1);
-  SP_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, w.bx, rp1, ro(0, h->g1a, h->b1a, 1), st));
+  const float* W1a = h->wbuf + h->woff[layer_index(h, open ? "backbone.0.0.conv.weight" : "conv1a.weight")];
+  const float* B1a = h->wbuf + h->woff[layer_index(h, open ? "backbone.0.0.conv.bias" : "conv1a.bias")];
+  // open: |relu(.) s + t| <= max|s| (g M + bmax) + max|t|
+  if (open)
+    SP_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, h->gbuf + h->s1a, h->gbuf + h->t1a, w.bx, rp1,
+                         ro(0, h->smax1a * h->g1a, h->smax1a * h->b1a + h->tmax1a, 1), st));
+  else
+    SP_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, nullptr, nullptr, w.bx, rp1, ro(0, h->g1a, h->b1a, 1), st));
 
   // encoder: (input image, its rows, K, spatial H x W, pool?) -> output
   struct Step { _Float16* x; _Float16* y; int H, W, Cin, Cout; bool pool; };
@@ -388,6 +485,11 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
     a.rtab = w.rtab;
     a.x_slot = x_slot;
     a.ro = ro(x_slot, m.g, m.bmax, y_slot);
+    if (open) {
+      a.post_scale = h->gbuf + m.soff;
+      a.post_shift = h->gbuf + m.toff;
+      a.ro = ro(x_slot, m.smax * m.g, m.smax * m.bmax + m.tmax, y_slot);
+    }
     a.pool = t.pool;
     SP_HIP(lg::sp_conv3x3(a, st));
     return LG_OK;
@@ -439,7 +541,7 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
     const int k = in->max_keypoints;
     SP_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, s.Hs * s.Ws, k, w.sel, out->keypoint_scores, s.cap, out->counts, st));
     SP_HIP(lg::sp_keypoints(w.sel, out->counts, B, s.cap, s.Hs, s.Ws, scores, c.refinement_radius, w.kp, st));
-    SP_HIP(lg::sp_sample(w.kp, out->counts, B, s.cap, w.desc, s.Hc, s.Wc, c.legacy_sampling, out->descriptors, out->keypoints,
+    SP_HIP(lg::sp_sample(w.kp, out->counts, B, s.cap, w.desc, s.Hc, s.Wc, h->sample_mode, out->descriptors, out->keypoints,
                          st));
     if (out->host_counts) {
       SP_HIP(hipMemcpyAsync(out->host_counts, out->counts, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -457,7 +559,7 @@ int sp_sample_descriptors(sp_handle_t* h, const float* keypoints, const int32_t*
   const Work w = carve((char*)workspace, h->last, std::max(Nh, 256));
   if (workspace_bytes < w.bytes) return fail(LG_E_WORKSPACE, "workspace too small");
   SP_HIP(hipSetDevice(h->device));
-  SP_HIP(lg::sp_sample(keypoints, counts, B, capacity, w.desc, h->last.Hc, h->last.Wc, h->cfg.legacy_sampling, descriptors,
+  SP_HIP(lg::sp_sample(keypoints, counts, B, capacity, w.desc, h->last.Hc, h->last.Wc, h->sample_mode, descriptors,
                        nullptr, (hipStream_t)stream));
   return LG_OK;
 }

@@ -8,7 +8,8 @@ model registry that resolve the matcher by name.
   ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
   HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.depth_matcher"`` to the
   pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
-  the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`).  Other components (filters,
+  the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
+  the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -164,6 +165,12 @@ def _superpoint():
     return SuperPoint
 
 
+def _superpoint_open():
+    from .superpoint_open import SuperPoint
+
+    return SuperPoint
+
+
 def _superglue():
     from .superglue import SuperGlue
 
@@ -188,7 +195,7 @@ def _nn_matcher():
     return NearestNeighborMatcher
 
 
-_LAZY = (_superpoint, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
+_LAZY = (_superpoint, _superpoint_open, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -200,6 +207,9 @@ _REGISTRY = {
     "gluefactory_nonfree.superpoint": _superpoint,
     "extractors.superpoint": _superpoint,
     "superpoint": _superpoint,
+    # the open (MIT) SuperPoint (models/extractors/superpoint_open.py), resolved lazily
+    "extractors.superpoint_open": _superpoint_open,
+    "superpoint_open": _superpoint_open,
     # the SuperGlue matcher (gluefactory_nonfree/superglue.py), resolved lazily
     "gluefactory_nonfree.superglue": _superglue,
     "superglue": _superglue,

@@ -75,6 +75,14 @@ class SuperPoint(nn.Module):
                              int(c.nms_radius), int(c.refinement_radius), int(c.remove_borders or 0),
                              int(bool(c.legacy_sampling)), float(c.detection_threshold))
 
+    def _create_handle(self, lib, device, h):
+        cfg = self._lib_config()
+        _lib.check(lib.sp_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sp_create")
+
+    def _native_state(self):
+        """The tensors sp_load_weights takes, by schema name."""
+        return self.state_dict(keep_vars=True)
+
     def _weights_signature(self):
         return tuple((id(m), n, t.data_ptr(), t._version) for m in self.modules() for n, t in m._parameters.items()
                      if t is not None)
@@ -86,12 +94,11 @@ class SuperPoint(nn.Module):
             self._handle = None
         if self._handle is None:
             h = ctypes.c_void_p()
-            cfg = self._lib_config()
-            _lib.check(lib.sp_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sp_create")
+            self._create_handle(lib, device, h)
             self._handle, self._handle_device, self._weights_key = h, device, None
         key = self._weights_signature()
         if key != self._weights_key:
-            sd = self.state_dict(keep_vars=True)
+            sd = self._native_state()
             names = list(sd)
             ts = []
             for n in names:
@@ -180,7 +187,18 @@ class SuperPoint(nn.Module):
             pred["descriptors"] = dense_desc.permute(0, 3, 1, 2)  # [B, D, Hc, Wc] view of the NHWC map
         if not sparse:
             return pred
-        n = list(host_counts)
+        out_pred = self._sparse_pred(lib, data, image, kpts, scores, desc, counts, list(host_counts), max_kps, cap, ws, nb,
+                                     stream)
+        if c.dense_outputs:
+            out_pred["dense_descriptors"] = pred["descriptors"]
+        return out_pred
+
+    def _sparse_pred(self, lib, data, image, kpts, scores, desc, counts, n, max_kps, cap, ws, nb, stream):
+        """Keypoints, scores and descriptors of an sp_forward as the module's outputs: padded to
+        max_kps (force_num_keypoints), ragged (data["ragged_keypoints"]) or stacked."""
+        c = self.conf
+        device = image.device
+        B = image.shape[0]
         n_max = max(n)
         if c.force_num_keypoints:
             kp = kpts[:, :max(n_max, max_kps)] - 0.5  # back to the sampling frame (+0.5 is exact)
@@ -220,8 +238,6 @@ class SuperPoint(nn.Module):
                 _lib.check(lib.sp_sample_descriptors(self._handle, _ptr(kp), _ptr(cnt), B, k, _ptr(desc), _ptr(ws), nb,
                                                      stream), "sp_sample_descriptors")
             out_pred = {"keypoints": kpts[:, :k], "keypoint_scores": scores[:, :k], "descriptors": desc[:, :k]}
-        if c.dense_outputs:
-            out_pred["dense_descriptors"] = pred["descriptors"]
         return out_pred
 
     def _pad(self, kp, scores, n, length, data, image):

@@ -62,7 +62,28 @@ typedef struct {
 int sp_create(const sp_config_t* cfg, int device, sp_handle_t** out);
 int sp_destroy(sp_handle_t* h);
 
-/* State-dict schema (superpoint.py:179-196): conv1a..conv4b, convPa/convPb, convDa/convDb. */
+/* The open (MIT-licensed) SuperPoint, gluefactory/models/extractors/superpoint_open.py:76-207:
+ * the same ten convolutions, each block conv -> ReLU -> BatchNorm(eps 1e-3, running statistics)
+ * with the 2x2 pools after the BatchNorm, 1x1 heads conv -> BatchNorm, descriptors sampled with
+ * grid_sample(align_corners=False) at (k + 0.5) / (8 size).  channels is fixed to
+ * [64, 64, 128, 128, 256].  The handle is an sp_handle_t: every function of this header works on
+ * it, with these differences:
+ *   - the state-dict schema is the 12 blocks backbone.{0..3}.{0,1}, detector.{0,1},
+ *     descriptor.{0,1} x {conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
+ *     bn.running_var} (72 fp32 tensors; bn.num_batches_tracked is int64 and is not passed);
+ *   - sp_forward needs sparse = 1 and image_size = NULL (borders are removed at the map's edges);
+ *   - a negative detection_threshold keeps every NMS-suppressed pixel as a candidate of score 0. */
+typedef struct {
+  int32_t descriptor_dim;      /* 256 (the only value the kernels support) */
+  int32_t nms_radius;          /* 4 (0..8) */
+  int32_t remove_borders;      /* 4 (0 = off) */
+  float detection_threshold;   /* 0.005, strict '>' */
+} sp_open_config_t;
+
+int sp_open_create(const sp_open_config_t* cfg, int device, sp_handle_t** out);
+
+/* State-dict schema (superpoint.py:179-196): conv1a..conv4b, convPa/convPb, convDa/convDb
+ * (an sp_open_create handle: the 72 tensors listed above). */
 int sp_weight_count(const sp_handle_t* h);
 const char* sp_weight_name(const sp_handle_t* h, int index);
 int64_t sp_weight_numel(const sp_handle_t* h, int index);

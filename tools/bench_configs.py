@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-GPU measurements of the BASELINE.json configs other than the headline one (bench.py).
 
-    python tools/bench_configs.py [--only 1,3,4,sp,sg,e2e] [--reps R]
+    python tools/bench_configs.py [--only 1,3,4,sp,spo,sg,e2e] [--reps R]
 
 One JSON line per config:
   configs[1]  N=1024, 9 layers, B=1 (latency-shaped: one pair per forward)
@@ -10,6 +10,7 @@ One JSON line per config:
               B == 1, lightglue.py:528,533); MegaDepth-like 1600x1200 keypoints; also the same
               batch unpruned and one pair per forward
   sp          SuperPoint (§8f row 3): 16 gray 640x480 images per forward, top-2048 keypoints
+  spo         the open SuperPoint (extractors.superpoint_open), shaped like sp
   e2e         configs[2] end to end: SuperPoint on both views + LightGlue, 32 pairs per forward
   configs[4]  N=4096, 8 pairs per GPU (64 over 8 GPUs): the LightGlue forward at N=4096 and the
               SuperGlue log-domain Sinkhorn (superglue.py:173-201, 50 iterations) on the
@@ -149,6 +150,24 @@ def cfg_sp(dev, reps, B=16, H=480, W=640, k=2048):
             "keypoints": list(pred["keypoints"].shape)}
 
 
+def cfg_spo(dev, reps, B=16, H=480, W=640, k=2048):
+    """The open SuperPoint (extractors.superpoint_open), shaped like `sp`: B gray 640x480 images per
+    forward, top-2048 keypoints, recipe weights.  The same ten convolutions, so the same flops."""
+    from lightglue_amd import SuperPointOpen
+    from lightglue_amd.sp_weights import superpoint_open_state_dict, synthetic_images
+
+    m = SuperPointOpen({"max_num_keypoints": k}).eval().to(dev)
+    m.load_state_dict({n: torch.from_numpy(v) if v.ndim else torch.tensor(int(v))
+                       for n, v in superpoint_open_state_dict(seed=0).items()}, strict=True)
+    img = torch.from_numpy(synthetic_images(B, 1, H, W, seed=1)).to(dev)
+    with torch.no_grad():
+        s, pred = timed(lambda: m({"image": img}), reps)
+    fl = sp_flops(H, W) * B
+    return {"config": f"SuperPoint-open {W}x{H} gray, batch={B}, max_num_keypoints={k}", "value": round(B / s, 2),
+            "unit": "images/s", "ms_per_image": round(1e3 * s / B, 3), "dense_tflops_wall": round(fl / s / 1e12, 1),
+            "keypoints": list(pred["keypoints"].shape)}
+
+
 def sg_flops(B, M, N, L=18, D=256):
     """Dense flops of a SuperGlue forward (GNN + final_proj + cost; the encoder and Sinkhorn are
     not counted): per layer q/k/v + mlp.0 (merge folded) + mlp.3 on both images, attention
@@ -214,7 +233,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    fns = {"1": cfg1, "3": cfg3, "4": cfg4, "sp": cfg_sp, "sg": cfg_sg, "e2e": cfg_e2e}
+    fns = {"1": cfg1, "3": cfg3, "4": cfg4, "sp": cfg_sp, "spo": cfg_spo, "sg": cfg_sg, "e2e": cfg_e2e}
     for k in a.only.split(","):
         print(json.dumps(fns[k](dev, a.reps)), flush=True)
 
