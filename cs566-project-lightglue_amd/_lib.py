@@ -98,6 +98,10 @@ EXPORTED_SYMBOLS = [
 KERNEL_IDS = {"attention": 0, "gemm": 1, "assign": 2}
 # lg_config_t.precision (include/lightglue_mi355x.h): "auto" = fp16x3 (device-side range scaling)
 PRECISIONS = {"auto": 0, "bf16x6": 1}
+# flag on "auto" (LG_PREC_ATTN_F16): the eval forward's attention in half precision, conf "flash"
+PREC_ATTN_F16 = 0x100
+# lg_outputs_t.precision_used -> LightGlue.last_precision_used
+PRECISION_NAMES = {0: "fp16x3", 1: "bf16x6", PREC_ATTN_F16: "fp16x3+fp16attn"}
 
 
 class LGConfig(ctypes.Structure):

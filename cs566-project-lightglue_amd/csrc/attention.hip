@@ -1,5 +1,6 @@
 // Flash-style fp32-accurate attention on gfx950 matrix cores: fp16x3 (PREC_H3, default) and
-// bf16x6 (PREC_X6) operand formats, see common.h.
+// bf16x6 (PREC_X6) operand formats, see common.h; and the fp16 attention of `flash: true` (PREC_H1:
+// the fp16x3 kernel's walk with one fp16 MFMA per product).
 //
 //   O = softmax(Q K^T * scale) V      per (set, pair, head); never materialises the N x N scores.
 //
@@ -377,7 +378,12 @@ __device__ __forceinline__ float sum_x16_32(float v) {
 // workgroup each; instead of the context the workgroup writes its unnormalised partial (O, the
 // softmax reference m, the 2^11-scaled sum l and the query's exponent factor c) and
 // attn_split_combine_kernel merges the ranges.
-template <int SUBS, int PRIO, int WAVES = 8, bool SPLIT = false, bool QP = false>
+// H1 (PREC_H1, "fp16 attention"): the same walk with every product a single fp16 MFMA -- scores
+// K_h . y_h (y_h the one fp16 rounding of the query the split forms anyway: yhs), O += V_h^T . hs
+// (hs = fp16(e)).  Only the high planes of K and V are staged (an LDS tile is half the size), the
+// ql / qh query pieces and P's low piece are not built; the softmax, its fp32 l / O accumulators,
+// the split partials and the context image are those of the fp16x3 numerics.
+template <int SUBS, int PRIO, int WAVES = 8, bool SPLIT = false, bool QP = false, bool H1 = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_kernel(AttnSet s0, AttnSet s1, int B, int H, int nqb,
                                                                 float scale_log2e, float* part = nullptr,
                                                                 int nsplit = 1, int lsplit = 0) {
@@ -386,11 +392,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
   constexpr int LT = KT * SUBS;            // keys per LDS tile (one barrier)
   constexpr int NKT = KT / 16;
   constexpr int PL = LT * kHeadDim;        // one plane of an LDS tile (elements)
-  constexpr int PIECES = 4 * LT / 8;       // 1 KiB LDS-DMA pieces per tile (K h/l, V h/l; 8 rows each)
+  constexpr int NPL = H1 ? 1 : 2;          // planes staged per tensor (H1: the high plane only)
+  constexpr int PIECES = 2 * NPL * LT / 8; // 1 KiB LDS-DMA pieces per tile (K h/l, V h/l; 8 rows each)
   constexpr int PPW = PIECES / WAVES;
   static_assert(PIECES % WAVES == 0, "pieces per wave");
-  __shared__ __attribute__((aligned(16))) _Float16 Ks[2 * 2 * PL];
-  __shared__ __attribute__((aligned(16))) _Float16 Vs[2 * 2 * PL];
+  __shared__ __attribute__((aligned(16))) _Float16 Ks[2 * NPL * PL];
+  __shared__ __attribute__((aligned(16))) _Float16 Vs[2 * NPL * PL];
 
   int item = LG_ATTN_REVERSE ? xcd_chunk_rev(blockIdx.x, gridDim.x) : xcd_chunk(blockIdx.x, gridDim.x);
   int split = 0;
@@ -433,7 +440,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, g = lane >> 4;
 
-  f16x8 qh[2][2], qhs[2][2], ql[2][2];
+  [[maybe_unused]] f16x8 qh[2][2], qhs[2][2], ql[2][2];  // H1 builds qhs only
   float c_lane[2];
   const int ek = range_slot_exp(S.rtab, S.k_slot);  // key planes hold k * 2^-ek (RangeOut)
   // Query pieces, two forms (mfma_h3_16 computes x_l yh + x_h yl + x_h yhs, the key planes being
@@ -488,16 +495,20 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
         _Float16 h, l;
         if (exact) {
           split2h(ldexpf(xv, exq[qt]), h, l);
-          qh[qt][ks][e] = h;
-          ql[qt][ks][e] = l;
+          if constexpr (!H1) {
+            qh[qt][ks][e] = h;
+            ql[qt][ks][e] = l;
+          }
           qhs[qt][ks][e] = h * (_Float16)kLoScale;
         } else {
           const float y = xv * ysc;
           h = (_Float16)y;
           l = (_Float16)(y - (float)h);  // exact difference, rounded (subnormal when tiny)
           qhs[qt][ks][e] = h;
-          ql[qt][ks][e] = l;
-          qh[qt][ks][e] = (_Float16)((float)h * (1.f / kLoScale));
+          if constexpr (!H1) {
+            ql[qt][ks][e] = l;
+            qh[qt][ks][e] = (_Float16)((float)h * (1.f / kLoScale));
+          }
         }
       }
   }
@@ -516,7 +527,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
       const int c = isv ? cs ^ (((r >> 1) & 3) << 1) : cs ^ ((r >> 1) & 7);
       const _Float16* base = (isv ? Vp : Kp) + (size_t)pl * ps + (size_t)t0 * kHeadDim;
       const uint32_t voff = (uint32_t)((min(t0 + r, Nk - 1) - t0) * kHeadDim + c * 8) * 2u;
-      const uint32_t dst = (isv ? vs_lds : ks_lds) + (uint32_t)(((buf * 2 + pl) * PL + (qq % (LT / 8)) * 8 * kHeadDim) * 2);
+      const uint32_t dst = (isv ? vs_lds : ks_lds) + (uint32_t)(((buf * NPL + pl) * PL + (qq % (LT / 8)) * 8 * kHeadDim) * 2);
       dma16_u(base, voff, dst);
     }
   };
@@ -541,7 +552,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
       const int qq = isv ? q - PIECES / 2 : q;
       const int pl = qq / (LT / 8);
       const _Float16* base = (isv ? Vp : Kp) + (size_t)pl * ps + (size_t)t0 * kHeadDim;
-      const uint32_t dst = (isv ? vs_lds : ks_lds) + (uint32_t)(((buf * 2 + pl) * PL + (qq % (LT / 8)) * 8 * kHeadDim) * 2);
+      const uint32_t dst = (isv ? vs_lds : ks_lds) + (uint32_t)(((buf * NPL + pl) * PL + (qq % (LT / 8)) * 8 * kHeadDim) * 2);
       dma16_u(base, voff_full[i], dst);
     }
   };
@@ -586,14 +597,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
     const _Float16* Kc = Ks + r16 * kHeadDim + off;
     const _Float16* Vc = Vs + vrow * kHeadDim + 4 * (vp4 & 1) + off;
 
-    f16x8 kf[NKT][2][2];
+    f16x8 kf[NKT][2][NPL];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const int off = kt * 16 * kHeadDim + kcol[ks];
         kf[kt][ks][0] = *reinterpret_cast<const f16x8*>(Kc + off);
-        kf[kt][ks][1] = *reinterpret_cast<const f16x8*>(Kc + PL + off);
+        if constexpr (!H1) kf[kt][ks][1] = *reinterpret_cast<const f16x8*>(Kc + PL + off);
       }
     asm volatile("" ::: "memory");
     f32x4 sc[NKT][2];
@@ -603,16 +614,19 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
       for (int qt = 0; qt < 2; ++qt) {
         f32x4 a = EXACT ? f32x4{0.f, 0.f, 0.f, 0.f} : cm[qt];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a = mfma_h3_16(kf[kt][ks][0], kf[kt][ks][1], qhs[qt][ks], ql[qt][ks], qh[qt][ks], a);
+        for (int ks = 0; ks < 2; ++ks) {
+          if constexpr (H1) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kt][ks][0], qhs[qt][ks], a, 0, 0, 0);
+          else a = mfma_h3_16(kf[kt][ks][0], kf[kt][ks][1], qhs[qt][ks], ql[qt][ks], qh[qt][ks], a);
+        }
         sc[kt][qt] = a;
       }
-    f16x8 vf[NKT / 2][4][2];
+    f16x8 vf[NKT / 2][4][NPL];
 #pragma unroll
     for (int p = 0; p < NKT / 2; ++p)
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
+        for (int pl = 0; pl < NPL; ++pl) {
           const f16x4 lo = tr_read_h(Vc + pl * PL + (32 * p) * kHeadDim + vcol[dt]);
           const f16x4 hi = tr_read_h(Vc + pl * PL + (32 * p + 16) * kHeadDim + vcol[dt]);
           vf[p][dt][pl] = f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -715,18 +729,26 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
       for (int qt = 0; qt < 2; ++qt) {
         // P pieces at scale 2^11: phs = fp16(e), pl = fp16(e - phs); the value planes' low piece is
         // unscaled (split2h_v), so v_h phs + v_h pl + v_l phs = 2^11 (v_h p_h + v_h p_l + v_l p_h)
-        f16x8 phs, pl;
+        // H1: P is its one fp16 rounding, O += V_h^T . phs
+        [[maybe_unused]] f16x8 phs, pl;
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {
           const float e0 = sc[2 * p + (j >> 2)][qt][j & 3];
           const float e1 = sc[2 * p + (j >> 2)][qt][(j & 3) + 1];
           const f16x2 hs = {(_Float16)e0, (_Float16)e1};
-          const f16x2 lo = lo_pair(e0, e1, hs);
-          phs[j] = hs[0]; phs[j + 1] = hs[1];
-          pl[j] = lo[0]; pl[j + 1] = lo[1];
+          if constexpr (H1) {
+            phs[j] = hs[0]; phs[j + 1] = hs[1];
+          } else {
+            const f16x2 lo = lo_pair(e0, e1, hs);
+            phs[j] = hs[0]; phs[j + 1] = hs[1];
+            pl[j] = lo[0]; pl[j + 1] = lo[1];
+          }
         }
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt][qt] = mfma_h3_16(vf[p][dt][0], vf[p][dt][1], phs, pl, phs, o[dt][qt]);
+        for (int dt = 0; dt < 4; ++dt) {
+          if constexpr (H1) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[p][dt][0], phs, o[dt][qt], 0, 0, 0);
+          else o[dt][qt] = mfma_h3_16(vf[p][dt][0], vf[p][dt][1], phs, pl, phs, o[dt][qt]);
+        }
       }
   };
 
@@ -734,11 +756,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
   using Mask = std::integral_constant<bool, true>;
   const int nlt = (Nk + LT - 1) / LT;
   const int nfull = Nk / LT;  // LDS tiles without a ragged end
-  using IC0 = std::integral_constant<int, 0>;
-  using IC1 = std::integral_constant<int, KT * kHeadDim>;
-  using IC2 = std::integral_constant<int, 2 * PL>;
-  using IC3 = std::integral_constant<int, 2 * PL + KT * kHeadDim>;
-  static_assert(SUBS == 1 || SUBS == 2, "sub-tiles per LDS tile");
+  // LDS element offsets of sub-tile s of buffer 0 (A) and buffer 1 (B)
+  using A0 = std::integral_constant<int, 0>;
+  using A1 = std::integral_constant<int, KT * kHeadDim>;
+  using A2 = std::integral_constant<int, 2 * KT * kHeadDim>;
+  using A3 = std::integral_constant<int, 3 * KT * kHeadDim>;
+  using B0 = std::integral_constant<int, NPL * PL>;
+  using B1 = std::integral_constant<int, NPL * PL + KT * kHeadDim>;
+  using B2 = std::integral_constant<int, NPL * PL + 2 * KT * kHeadDim>;
+  using B3 = std::integral_constant<int, NPL * PL + 3 * KT * kHeadDim>;
+  static_assert(SUBS == 1 || SUBS == 2 || SUBS == 4, "sub-tiles per LDS tile");
   // static priority for the second-dispatched half (MI355X_MICROARCH.md, two waves per SIMD, item 4)
   if (PRIO && wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
   issue(0, 0);
@@ -752,12 +779,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
     int t = 0;                                                                      \
     for (; t + 2 <= nfull; t += 2) {                                                \
       /* buffer 1 released by the barrier; t+1 < nfull */                           \
-      body(IC0{}, NoMask{}, EXc, t * LT, 1, (t + 1) * LT, 1);                       \
-      if constexpr (SUBS == 2) body(IC1{}, NoMask{}, EXc, t * LT + KT, 0, 0, 0);    \
+      body(A0{}, NoMask{}, EXc, t * LT, 1, (t + 1) * LT, 1);                        \
+      if constexpr (SUBS >= 2) body(A1{}, NoMask{}, EXc, t * LT + KT, 0, 0, 0);     \
+      if constexpr (SUBS == 4) body(A2{}, NoMask{}, EXc, t * LT + 2 * KT, 0, 0, 0); \
+      if constexpr (SUBS == 4) body(A3{}, NoMask{}, EXc, t * LT + 3 * KT, 0, 0, 0); \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                              \
       __syncthreads();                                                              \
-      body(IC2{}, NoMask{}, EXc, (t + 1) * LT, t + 2 < nfull ? 1 : (t + 2 < nlt ? 2 : 0), (t + 2) * LT, 0); \
-      if constexpr (SUBS == 2) body(IC3{}, NoMask{}, EXc, (t + 1) * LT + KT, 0, 0, 0); \
+      body(B0{}, NoMask{}, EXc, (t + 1) * LT, t + 2 < nfull ? 1 : (t + 2 < nlt ? 2 : 0), (t + 2) * LT, 0); \
+      if constexpr (SUBS >= 2) body(B1{}, NoMask{}, EXc, (t + 1) * LT + KT, 0, 0, 0); \
+      if constexpr (SUBS == 4) body(B2{}, NoMask{}, EXc, (t + 1) * LT + 2 * KT, 0, 0, 0); \
+      if constexpr (SUBS == 4) body(B3{}, NoMask{}, EXc, (t + 1) * LT + 3 * KT, 0, 0, 0); \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                              \
       __syncthreads();                                                              \
     }                                                                               \
@@ -766,7 +797,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void attention_h3g_
       if (t + 1 < nlt) issue((t + 1) * LT, buf ^ 1);                                \
       for (int sub = 0; sub < SUBS; ++sub) {                                        \
         const int s0 = t * LT + sub * KT;                                           \
-        if (s0 < Nk) body(buf * 2 * PL + sub * KT * kHeadDim, Mask{}, EXc, s0, 0, 0, 0); \
+        if (s0 < Nk) body(buf * NPL * PL + sub * KT * kHeadDim, Mask{}, EXc, s0, 0, 0, 0); \
       }                                                                             \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                              \
       __syncthreads();                                                              \
@@ -885,7 +916,7 @@ __global__ __launch_bounds__(256) void attn_split_combine_kernel(AttnSet s0, Att
   *reinterpret_cast<f16x8*>(S.op + S.ops + off) = lo;
 }
 
-template <int SUBS, int PRIO = 0, int WAVES = 8>
+template <int SUBS, int PRIO = 0, int WAVES = 8, bool H1 = false>
 static hipError_t attention_h3g_launch(const AttnSet& s0, const AttnSet& s1, int B, int H, float scale, hipStream_t st,
                                        bool qp, float* part = nullptr, int nsplit = 1) {
   constexpr int QB = 32 * WAVES;
@@ -899,11 +930,11 @@ static hipError_t attention_h3g_launch(const AttnSet& s0, const AttnSet& s1, int
     const int nk = s0.Nk > s1.Nk ? s0.Nk : s1.Nk;
     const int lsplit = ((nk + nsplit - 1) / nsplit + LT - 1) / LT * LT;
     if (qp)
-      hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, true, true>), dim3(items * nsplit), dim3(64 * WAVES), 0, st,
-                         s0, s1, B, H, nqb, scale * 1.4426950408889634f, part, nsplit, lsplit);
+      hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, true, true, H1>), dim3(items * nsplit), dim3(64 * WAVES), 0,
+                         st, s0, s1, B, H, nqb, scale * 1.4426950408889634f, part, nsplit, lsplit);
     else
-      hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, true>), dim3(items * nsplit), dim3(64 * WAVES), 0, st, s0,
-                         s1, B, H, nqb, scale * 1.4426950408889634f, part, nsplit, lsplit);
+      hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, true, false, H1>), dim3(items * nsplit), dim3(64 * WAVES), 0,
+                         st, s0, s1, B, H, nqb, scale * 1.4426950408889634f, part, nsplit, lsplit);
     const size_t threads = (size_t)2 * B * H * nq * 8;
     const dim3 cg((unsigned)((threads + 255) / 256)), cb(256);
     switch (nsplit) {
@@ -914,11 +945,11 @@ static hipError_t attention_h3g_launch(const AttnSet& s0, const AttnSet& s1, int
     return hipGetLastError();
   }
   if (qp)
-    hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, false, true>), dim3(items), dim3(64 * WAVES), 0, st, s0, s1, B,
-                       H, nqb, scale * 1.4426950408889634f);
+    hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, false, true, H1>), dim3(items), dim3(64 * WAVES), 0, st, s0, s1,
+                       B, H, nqb, scale * 1.4426950408889634f);
   else
-    hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES>), dim3(items), dim3(64 * WAVES), 0, st, s0, s1, B, H, nqb,
-                       scale * 1.4426950408889634f);
+    hipLaunchKernelGGL((attention_h3g_kernel<SUBS, PRIO, WAVES, false, false, H1>), dim3(items), dim3(64 * WAVES), 0, st, s0,
+                       s1, B, H, nqb, scale * 1.4426950408889634f);
   return hipGetLastError();
 }
 
@@ -1336,8 +1367,29 @@ size_t attention_split_floats(int B, int H, int nq, int nk) {
   return ns > 1 ? (size_t)ns * 2 * B * H * nq * (kHeadDim + 4) : 0;
 }
 
+#ifndef LG_ATTN_H1_SUBS
+// 64-key steps per LDS tile of the fp16 attention (PREC_H1): 2 (2 x 32 KiB, two 8-wave workgroups
+// per CU) or 4 (2 x 64 KiB, one); DESIGN.md §5 "fp16 attention" has the A/B
+#define LG_ATTN_H1_SUBS 2
+#endif
+
 hipError_t attention_f32(const AttnSet& s0, const AttnSet& s1, int B, int H, float scale, int prec, hipStream_t st,
                          float* part, size_t part_floats, bool q_planes) {
+  if (prec == PREC_H1) {  // the h3g walk on single fp16 products (no h3m form)
+    if (!s0.op || !s1.op || !s0.q || !s1.q) return hipErrorInvalidValue;
+    const int nq = s0.Nq > s1.Nq ? s0.Nq : s1.Nq;
+    constexpr int SUBS = LG_ATTN_H1_SUBS;
+    switch (attention_waves(B, H, nq)) {
+      case 2: return attention_h3g_launch<SUBS, 1, 2, true>(s0, s1, B, H, scale, st, q_planes);
+      case 4: {
+        const int nk = s0.Nk > s1.Nk ? s0.Nk : s1.Nk;
+        const int ns = attention_nsplit(B, H, nq, nk);
+        const bool fits = part && part_floats >= attention_split_floats(B, H, nq, nk);
+        return attention_h3g_launch<SUBS, 1, 4, true>(s0, s1, B, H, scale, st, q_planes, fits ? part : nullptr, fits ? ns : 1);
+      }
+      default: return attention_h3g_launch<SUBS, 1, 8, true>(s0, s1, B, H, scale, st, q_planes);
+    }
+  }
   if (prec == PREC_H3) {
     if (!s0.op || !s1.op || !s0.q || !s1.q) return hipErrorInvalidValue;
     const int nq = s0.Nq > s1.Nq ? s0.Nq : s1.Nq;

@@ -18,7 +18,10 @@ enum EpiKind {
 //            scaled by a per-tensor power of two chosen on the device (RangeOut below), so the
 //            fp16 range cannot be exceeded and no host check is needed
 //   PREC_X6  bf16x6 -- 6 bf16 MFMAs per product; full fp32 range
-enum Prec { PREC_H3 = 0, PREC_X6 = 1 };
+// and one that is not fp32-accurate, for attention_f32 only (the reference's `flash: true`):
+//   PREC_H1  fp16 attention -- the PREC_H3 plane images and softmax, each product ONE fp16 MFMA on
+//            the high planes (q, k, v and P rounded to fp16 once; fp32 accumulation and statistics)
+enum Prec { PREC_H3 = 0, PREC_X6 = 1, PREC_H1 = 2 };
 
 // ---- Point pruning and early stop for any batch size (lightglue.py:527-562,586-606) --------
 // The row space keeps a fixed slot per (image, pair): segment s < B is image 0 of pair s (rows

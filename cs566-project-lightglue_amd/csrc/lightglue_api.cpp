@@ -450,6 +450,10 @@ int lg_create(const lg_config_t* cfg, int device, lg_handle_t** out) {
     return fail(LG_E_INVALID, "head_dim must be 64 (descriptor_dim / num_heads)");
   if (cfg->n_layers < 1) return fail(LG_E_INVALID, "n_layers must be >= 1");
   if (cfg->input_dim <= 0 || cfg->input_dim % 32) return fail(LG_E_INVALID, "input_dim must be a positive multiple of 32");
+  if (cfg->precision == (LG_PREC_X6 | LG_PREC_ATTN_F16))
+    return fail(LG_E_INVALID, "precision: LG_PREC_ATTN_F16 (fp16 attention) goes with LG_PREC_AUTO only, not with LG_PREC_X6");
+  if ((cfg->precision & ~LG_PREC_ATTN_F16) != LG_PREC_AUTO && cfg->precision != LG_PREC_X6)
+    return fail(LG_E_INVALID, "precision: unknown value " + std::to_string(cfg->precision));
   LG_HIP(hipSetDevice(device));
   lg_handle* h = new lg_handle();
   h->cfg = *cfg;
@@ -739,7 +743,9 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   auto image = [&](_Float16* p, int K) { return PlaneRef{p, (long long)RP * K, RP}; };
   auto attn = [&](const AttnSet& a0, const AttnSet& a1, float scale, bool cross, bool q_planes) -> hipError_t {
     const int p = h->prof_begin(LG_KERNEL_ATTENTION, st);
-    const hipError_t e = attention_f32(a0, a1, B, H, scale, prec, st, w.apart, w.apart_floats, q_planes);
+    // fp16 attention (LG_PREC_ATTN_F16) reads the fp16x3 forward's planes: everything else is PREC_H3
+    const int aprec = prec == PREC_H3 && (c.precision & LG_PREC_ATTN_F16) ? PREC_H1 : prec;
+    const hipError_t e = attention_f32(a0, a1, B, H, scale, aprec, st, w.apart, w.apart_floats, q_planes);
     // self: 2 matmuls per image (QK^T, PV); cross: one shared sim + two PV (lightglue.py:236-242)
     const double hd = 64.0 * H * B;
     const double fl = cross ? 6.0 * a0.Nq * a0.Nk * hd : 4.0 * hd * ((double)a0.Nq * a0.Nk + (double)a1.Nq * a1.Nk);
@@ -1062,7 +1068,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       }
     }
   }
-  out->precision_used = prec;
+  out->precision_used = prec == PREC_H3 ? (c.precision & LG_PREC_ATTN_F16) : LG_PREC_X6;
   if (slots_overflow) return fail(LG_E_INTERNAL, "range table exhausted (internal: range_slots undercounts)");
 
   // ---- assignment head of each pair's last executed layer (lightglue.py:549-551,
@@ -1422,7 +1428,10 @@ int lg_attention(const float* q, const float* k, const float* v, int32_t B, int3
   char* ws = static_cast<char*>(workspace);
   unsigned* rtab = reinterpret_cast<unsigned*>(ws);  // slots 0/1: max|k|, max|v|; 2/3: k, v planes
   const size_t n = (size_t)B * H * Nk * 64;
-  const int prec = precision == LG_PREC_X6 ? lg::PREC_X6 : lg::PREC_H3;
+  if (precision != LG_PREC_AUTO && precision != LG_PREC_X6 && precision != LG_PREC_ATTN_F16)
+    return fail(LG_E_INVALID, "bad precision");
+  const int prec = precision == LG_PREC_X6 ? lg::PREC_X6 : lg::PREC_H3;  // operand planes; the kernel: aprec
+  const int aprec = precision == LG_PREC_ATTN_F16 ? lg::PREC_H1 : prec;
   const int np = prec == lg::PREC_X6 ? 3 : 2;
   void* kp = ws + kv_off;
   void* vp = ws + kv_off + np * n * 2;
@@ -1440,7 +1449,7 @@ int lg_attention(const float* q, const float* k, const float* v, int32_t B, int3
   const lg::AttnSet s0{q, kp, vp, (long long)n, ctx, Nq, Nk, img, (long long)rp * 256, rp, 0, h3 ? rtab : nullptr, 2};
   lg::AttnSet s1 = s0;
   s1.Nq = 0;
-  LG_HIP(lg::attention_f32(s0, s1, B, H, scale, prec, st, reinterpret_cast<float*>(ws + part_off),
+  LG_HIP(lg::attention_f32(s0, s1, B, H, scale, aprec, st, reinterpret_cast<float*>(ws + part_off),
                            lg::attention_split_floats(B, H, Nq, Nk)));
   if (h3) LG_HIP(lg::image_to_rows(img, (long long)rp * 256, rp, 256, ctx, B * Nq, rtab, 3, st));
   LG_HIP(hipStreamSynchronize(st));

@@ -15,8 +15,13 @@ Deliberate behaviour differences from the reference:
   raising ``UnboundLocalError`` (:452-455);
 * ``ref_descriptors*`` is ``[B, 1, M', 256]`` in eval mode and ``[B, L, M, 256]`` (every layer) in
   training mode, as the reference (:521-524,572); training mode also turns early stop and pruning
-  off (:502-503).  The training path computes in fp32 whatever ``mp`` says (the reference's
-  autocast is not mirrored).
+  off (:502-503).  The training path computes in fp32 whatever ``mp`` and ``flash`` say (the
+  reference's autocast and its half-precision SDPA are not mirrored there).
+* ``flash: true`` (:139-145, :229-233) runs the eval forward's self- and cross-attention in half
+  precision, as the reference does: q, k, v and the probabilities are rounded to fp16 once and each
+  product is one fp16 MFMA, with fp32 accumulation and softmax statistics.  The context keeps its
+  fp32 bits (the reference rounds its SDPA output to fp16).  The GEMMs and the assignment stay
+  fp16x3; ``precision: "bf16x6"`` together with ``flash: true`` is rejected.
 * with pruning and B > 1, ``log_assignment`` and ``ref_descriptors*`` are per-pair LISTS (pair b's
   kept block; the reference asserts B == 1, :528,533); ``kept0/1`` and ``stop_layer`` give the
   per-pair counts.
@@ -124,7 +129,8 @@ def _ptr(t):
 
 # Extension keys (no reference counterpart).  "precision": matrix-core operand format of the HIP
 # kernels, both fp32-accurate -- "auto" (fp16x3, run-time operands range-scaled on the device) or "bf16x6"
-# (DESIGN.md §3).  "return_similarity": also return the final head's similarity md0 md1^T
+# (DESIGN.md §3); the reference's own "flash" key adds fp16 attention to "auto" (_lib.PREC_ATTN_F16).
+# "return_similarity": also return the final head's similarity md0 md1^T
 # [B, M, N] as pred["similarity"] (MatchAssignment's second output, lightglue.py:311,315; the input
 # of a Sinkhorn assignment head, configs[4]).
 EXTENSION_CONF = {"precision": "auto", "return_similarity": False}
@@ -417,6 +423,11 @@ class LightGlue(nn.Module):
         super().__init__()
         self.conf = conf = merge_conf(self.default_conf, conf)
         d, h, n = int(conf.descriptor_dim), int(conf.num_heads), int(conf.n_layers)
+        if bool(conf.flash) and str(conf.precision) == "bf16x6":
+            raise ValueError(
+                'lightglue_amd: "flash": true (fp16 attention) goes with "precision": "auto" only, not with '
+                '"precision": "bf16x6"'
+            )
         if conf.input_dim != conf.descriptor_dim:
             self.input_proj = nn.Linear(conf.input_dim, d, bias=True)
         else:
@@ -516,7 +527,8 @@ class LightGlue(nn.Module):
             float(c.depth_confidence),
             float(c.width_confidence),
             float(c.filter_threshold),
-            _lib.PRECISIONS[str(c.precision)],
+            # the training entry points ignore the flag, so one handle serves train() and eval()
+            _lib.PRECISIONS[str(c.precision)] | (_lib.PREC_ATTN_F16 if bool(c.flash) else 0),
         )
 
     def _ensure_handle(self, device, upload=True):
@@ -791,7 +803,7 @@ class LightGlue(nn.Module):
             lib.lg_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(self._ws), ws_bytes.value, ctypes.c_void_p(stream)),
             "lg_forward",
         )
-        self.last_precision_used = "fp16x3" if out.precision_used == 0 else "bf16x6"
+        self.last_precision_used = _lib.PRECISION_NAMES[out.precision_used]
         if c.width_confidence > 0 and not self.training:
             prune0, prune1 = p0, p1
         else:

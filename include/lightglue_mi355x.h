@@ -68,10 +68,17 @@ typedef struct {
                              *   LG_PREC_AUTO  fp16x3; run-time operands are written scaled by a
                              *                 per-tensor power of two chosen on the device, so
                              *                 any fp32 magnitude is handled without a host check
-                             *   LG_PREC_X6    bf16x6 */
+                             *   LG_PREC_X6    bf16x6
+                             * LG_PREC_AUTO may carry the flag LG_PREC_ATTN_F16 (the reference's
+                             * `flash: true`, lightglue.py:139-145, :229-233): self- and cross-
+                             * attention of lg_forward then run in half precision -- q, k, v and
+                             * the probabilities rounded to fp16 once, one fp16 MFMA per product,
+                             * fp32 accumulation and softmax statistics -- while the GEMMs and the
+                             * assignment stay fp16x3.  Not fp32-accurate (DESIGN.md §5 "fp16
+                             * attention").  The training entry points ignore the flag. */
 } lg_config_t;
 
-enum { LG_PREC_AUTO = 0, LG_PREC_X6 = 1 };
+enum { LG_PREC_AUTO = 0, LG_PREC_X6 = 1, LG_PREC_ATTN_F16 = 0x100 }; /* the flag ORs with LG_PREC_AUTO only */
 
 typedef struct {
   int32_t B, M, N;              /* pairs, keypoints in image 0 / image 1 */
@@ -134,7 +141,8 @@ typedef struct {
   int32_t* stop;                /* device [B] or NULL: last executed layer per pair (early stop) */
   int32_t stop_layer;           /* host out: last executed layer (of pair 0) */
   int32_t kept0, kept1;         /* host out: M', N' of pair 0 after width pruning (= M, N without) */
-  int32_t precision_used;       /* host out: 0 = fp16x3, 1 = bf16x6 (LG_PREC_X6) */
+  int32_t precision_used;       /* host out: 0 = fp16x3, 1 = bf16x6 (LG_PREC_X6), LG_PREC_ATTN_F16 =
+                                 * fp16x3 with fp16 attention */
   float* similarity;            /* device [B,M,N] or NULL: md0 md1^T of the final assignment head, the
                                  * second output of MatchAssignment.forward (lightglue.py:311,315;
                                  * the input of a Sinkhorn head, configs[4]); with pruning pair b's
@@ -296,7 +304,8 @@ int lg_nn_match(const float* desc0, const float* desc1, int32_t B, int32_t M, in
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
  * [B][Nq][256] (column h*64 + d), softmax(scale * q k^T) v.  precision LG_PREC_AUTO runs the fp16x3
- * kernel (k and v range-scaled on the device), LG_PREC_X6 the bf16x6 one.  Synchronises the
+ * kernel (k and v range-scaled on the device), LG_PREC_X6 the bf16x6 one, LG_PREC_ATTN_F16 (alone or
+ * with LG_PREC_AUTO) the fp16 attention on the fp16x3 kernel's planes.  Synchronises the
  * stream before returning.  Workspace: lg_attention_workspace_bytes. */
 int lg_attention_workspace_bytes(int32_t B, int32_t H, int32_t Nq, int32_t Nk, size_t* bytes);
 int lg_attention(const float* q, const float* k, const float* v, int32_t B, int32_t H, int32_t Nq,
