@@ -32,6 +32,10 @@ EXPORTED_SYMBOLS = [
     "lg_profile_read",
     "lg_attention_workspace_bytes",
     "lg_attention",
+    # kernel-level linear GEMM entry (ABI 12, no handle)
+    "lg_linear_workspace_bytes",
+    "lg_linear",
+    "lg_plane_roundtrip",
     "lg_assignment_workspace_bytes",
     "lg_assignment_head",
     # homography ground truth (ABI 12, no handle)
@@ -180,6 +184,67 @@ class LGOutputs(ctypes.Structure):
     ]
 
 
+LIN_EPI = {"store": 0, "qkv_rot": 1, "cross_qkv": 2, "ln_gelu": 3}  # LG_LIN_*
+
+
+class LGLinearArgs(ctypes.Structure):  # lg_linear_args_t
+    _fields_ = [
+        ("R", ctypes.c_int32),
+        ("K0", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("Nout", ctypes.c_int32),
+        ("A0", _P),
+        ("lda0", ctypes.c_int32),
+        ("A1", _P),
+        ("lda1", ctypes.c_int32),
+        ("W", _P),
+        ("bias", _P),
+        ("res", _P),
+        ("res2", _P),
+        ("res2_row0", ctypes.c_int32),
+        ("ldr", ctypes.c_int32),
+        ("out_scale", ctypes.c_float),
+        ("relu", ctypes.c_int32),
+        ("precision", ctypes.c_int32),
+        ("epi", ctypes.c_int32),
+        ("ln_route", ctypes.c_int32),
+        ("ln_g", _P),
+        ("ln_b", _P),
+        ("B", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("M", ctypes.c_int32),
+        ("N", ctypes.c_int32),
+        ("cosb", _P),
+        ("sinb", _P),
+        ("qk_scale", ctypes.c_float),
+        ("mask_B", ctypes.c_int32),
+        ("mask_M0", ctypes.c_int32),
+        ("mask_N0", ctypes.c_int32),
+        ("cnt", _P),
+        ("sel", _P),
+        ("sel_eq", ctypes.c_int32),
+        ("poison", ctypes.c_int32),
+        ("want_planes", ctypes.c_int32),
+        ("Y", _P),
+        ("Y2", _P),
+        ("y2_row0", ctypes.c_int32),
+        ("ldy", ctypes.c_int32),
+        ("yp", _P),
+        ("yp_rows", _P),
+        ("q", _P),
+        ("kp", _P),
+        ("vp", _P),
+        ("pstride", ctypes.c_int64),
+        ("exp_a0", ctypes.c_int32),
+        ("exp_a1", ctypes.c_int32),
+        ("exp_out", ctypes.c_int32),
+        ("exp_out_v", ctypes.c_int32),
+        ("max_out", ctypes.c_float),
+        ("max_out_v", ctypes.c_float),
+        ("bound_out", ctypes.c_float),
+    ]
+
+
 class SPConfig(ctypes.Structure):  # sp_config_t
     _fields_ = [
         ("has_detector", ctypes.c_int32),
@@ -322,6 +387,9 @@ def load():
             ctypes.c_int,
             [_P, _P, _P, i32, i32, i32, i32, ctypes.c_float, i32, _P, _P, sz, _P],
         ),
+        "lg_linear_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_linear": (ctypes.c_int, [ctypes.POINTER(LGLinearArgs), _P, sz, _P]),
+        "lg_plane_roundtrip": (ctypes.c_int, [_P, i32, i32, i32, i32, _P, ctypes.POINTER(i32), _P]),
         "lg_assignment_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_assignment_head": (ctypes.c_int, [_P, i32, _P, _P, i32, i32, i32, _P, _P, _P, _P, _P, sz, _P]),
         "lg_gt_homography_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),

@@ -312,6 +312,94 @@ int lg_attention(const float* q, const float* k, const float* v, int32_t B, int3
                  int32_t Nk, float scale, int32_t precision, float* ctx, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* Kernel-level entry (tests; the reference's counterpart is one nn.Linear with what the forward
+ * fuses behind it): one launch of the inference linear GEMM -- gemm_h3 (fp16x3, LG_PREC_AUTO) or
+ * gemm_x6 (bf16x6, LG_PREC_X6) -- on plain fp32 device tensors, prepared inside the workspace the
+ * way the forward prepares them.
+ *   Y = epilogue([A0 | A1] W^T + bias), A0 [R][K0] (row stride lda0), A1 [R][K-K0] (lda1; null when
+ *   K0 == K), W [Nout][K] (PyTorch Linear layout), bias [Nout] (nullable for LG_LIN_STORE / LN).
+ * fp16x3 preparation: a zeroed range table; max|A0|, max|A1| each into a slot of its own; each half
+ * written as a plane image with its own range exponent; the weight planes as at load time (scaled
+ * by 2^sw, max|W 2^sw| in [8, 16)); the output range bound from the weight's largest row L1 norm,
+ * max|bias| and max|res| (LG_LIN_LN_GELU: the LayerNorm bound; QKV: keys one-sided, values
+ * two-sided, as the forward builds them).
+ * epi:
+ *   LG_LIN_STORE      Y = relu?(res + (acc + bias) * out_scale); rows >= res2_row0 read res2 (when
+ *                     set), rows >= y2_row0 go to Y2 (when set).  fp32 rows (Y) and / or a plane
+ *                     image (want_planes: raw into yp, decoded into yp_rows).
+ *   LG_LIN_LN_GELU    GELU(LayerNorm_512(acc + bias) * ln_g + ln_b) as a plane image (yp, yp_rows);
+ *                     Nout == 512.  ln_route 0: the fused epilogue; 1: LG_LIN_STORE into fp32 and
+ *                     the LayerNorm + GELU row kernel (which does not look at the row mask).
+ *   LG_LIN_QKV_ROT    Nout == 768: q fp32 head-major [set][b][h][n][64] (rotary), k planes (rotary),
+ *                     v planes; cosb / sinb [R][32] (both null: no rotary).
+ *   LG_LIN_CROSS_QKV  Nout == 512: qk * qk_scale as planes (kp) and, when q is set, fp32 rows;
+ *                     v planes.
+ *   QKV: R == B * (M + N), H * 64 == 256, W and bias rows in the packed order c' = t*256 + h*64 + j,
+ *   j < 32 -> dim 2j, j >= 32 -> dim 2(j-32)+1; kp / vp hold 2 fp16 planes (keys h, l*2^11; values
+ *   h, l; times 2^exp) or 3 bf16 planes (h, m, l), pstride elements apart (>= R * 256).
+ * Row mask (cnt non-null): segments {mask_B, mask_M0, mask_N0} with mask_B * (M0 + N0) == R, live
+ * rows local < cnt[segment] and (sel null or sel[pair] == sel_eq).  Dead rows are never written.
+ * poison: after the A plane images are built, their dead and padding rows are filled with finite
+ * fp16 garbage of magnitude ~6e4 (stale workspace must not reach a live result).
+ * LG_PREC_X6 has no plane images: yp is not written, yp_rows receives the fp32 result; ln_route and
+ * poison are ignored, and the exponents come back 0.
+ * Host outputs: the range exponents of the A0 / A1 images, the output planes and the value planes,
+ * the recorded max |x| of the output / value planes, and bound_out (LG_LIN_LN_GELU: the LayerNorm
+ * bound the output exponent was chosen from).
+ * LG_E_INVALID (nothing launched, nothing written): Nout % 256, K % 32, K0 % 32, K0 <= 0 or > K,
+ * A1 null with K0 < K, a missing required pointer, lda / ldr / ldy not a multiple of 4 or a pointer
+ * off 16 bytes, an epilogue's shape rule.  LG_E_WORKSPACE: workspace smaller than
+ * lg_linear_workspace_bytes.  Synchronises the stream before returning. */
+enum { LG_LIN_STORE = 0, LG_LIN_QKV_ROT = 1, LG_LIN_CROSS_QKV = 2, LG_LIN_LN_GELU = 3 };
+typedef struct {
+  int32_t R, K0, K, Nout;
+  const float* A0;
+  int32_t lda0;
+  const float* A1;
+  int32_t lda1;
+  const float* W;
+  const float* bias;
+  const float* res;             /* [.][ldr] or NULL */
+  const float* res2;
+  int32_t res2_row0, ldr;
+  float out_scale;
+  int32_t relu;
+  int32_t precision;            /* LG_PREC_AUTO | LG_PREC_X6 */
+  int32_t epi;                  /* LG_LIN_* */
+  int32_t ln_route;
+  const float* ln_g;            /* [512] */
+  const float* ln_b;
+  int32_t B, H, M, N;           /* head layout (QKV) */
+  const float* cosb;
+  const float* sinb;
+  float qk_scale;
+  int32_t mask_B, mask_M0, mask_N0;
+  const int32_t* cnt;           /* device [2 * mask_B] or NULL: every row live */
+  const int32_t* sel;           /* device [mask_B] or NULL */
+  int32_t sel_eq;
+  int32_t poison;
+  int32_t want_planes;
+  float* Y;                     /* [.][ldy] or NULL */
+  float* Y2;
+  int32_t y2_row0, ldy;
+  void* yp;                     /* raw plane image: 2 planes [Nout / 32][rows_pad][32] fp16, rows_pad = R rounded up to 256 */
+  float* yp_rows;               /* [R][Nout] or NULL: the plane image decoded */
+  float* q;                     /* [R][256] head-major */
+  void* kp;
+  void* vp;
+  int64_t pstride;
+  int32_t exp_a0, exp_a1, exp_out, exp_out_v; /* host out */
+  float max_out, max_out_v, bound_out;        /* host out */
+} lg_linear_args_t;
+int lg_linear_workspace_bytes(int32_t R, int32_t K0, int32_t K, int32_t Nout, size_t* bytes);
+int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, void* stream);
+/* fp32 rows x [R][K] -> plane image (range exponent chosen on the device from max|x|, held to
+ * 2^(15 - lshift); two_sided: small tensors are scaled up too) -> fp32 rows out [R][K].
+ * *exponent (host): the exponent the planes were written with.  K % 32 == 0.  Allocates its own
+ * scratch; synchronises the stream. */
+int lg_plane_roundtrip(const float* x, int32_t R, int32_t K, int32_t lshift, int32_t two_sided, float* out,
+                       int32_t* exponent, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: the backward pass of LightGlue (the reference differentiates its forward with torch
  * autograd: gluefactory/train.py:436-450 over lightglue.py:444-579 and :614-663).  No reference
