@@ -36,6 +36,9 @@ EXPORTED_SYMBOLS = [
     "lg_linear_workspace_bytes",
     "lg_linear",
     "lg_plane_roundtrip",
+    # kernel-level assignment entry (ABI 12, no handle)
+    "lg_assign_workspace_bytes",
+    "lg_assign",
     "lg_assignment_workspace_bytes",
     "lg_assignment_head",
     # homography ground truth (ABI 12, no handle)
@@ -343,6 +346,37 @@ class SGOutputs(ctypes.Structure):  # sg_outputs_t
     ]
 
 
+ASSIGN_ROUTES = {"materialised": 0, "recomputed": 1}  # LG_ASSIGN_*
+ASSIGN_SENTINEL_F, ASSIGN_SENTINEL_I = -123.456, -77  # LG_ASSIGN_SENTINEL_F (as fp32) / _I
+
+
+class LGAssignArgs(ctypes.Structure):  # lg_assign_args_t
+    _fields_ = [
+        ("B", ctypes.c_int32),
+        ("M", ctypes.c_int32),
+        ("N", ctypes.c_int32),
+        ("md0", _P),
+        ("md1", _P),
+        ("sim", _P),
+        ("z0", _P),
+        ("z1", _P),
+        ("Mb", _P),
+        ("Nb", _P),
+        ("fixed", ctypes.c_int32),
+        ("raw_counts", ctypes.c_int32),
+        ("threshold", ctypes.c_float),
+        ("route", ctypes.c_int32),
+        ("poison", ctypes.c_int32),
+        ("la", _P),
+        ("m0", _P),
+        ("m1", _P),
+        ("s0", _P),
+        ("s1", _P),
+        ("exp_md", ctypes.c_int32),
+        ("max_md", ctypes.c_float),
+    ]
+
+
 class LightGlueLibError(RuntimeError):
     pass
 
@@ -390,6 +424,8 @@ def load():
         "lg_linear_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_linear": (ctypes.c_int, [ctypes.POINTER(LGLinearArgs), _P, sz, _P]),
         "lg_plane_roundtrip": (ctypes.c_int, [_P, i32, i32, i32, i32, _P, ctypes.POINTER(i32), _P]),
+        "lg_assign_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_assign": (ctypes.c_int, [ctypes.POINTER(LGAssignArgs), _P, sz, _P]),
         "lg_assignment_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_assignment_head": (ctypes.c_int, [_P, i32, _P, _P, i32, i32, i32, _P, _P, _P, _P, _P, sz, _P]),
         "lg_gt_homography_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),

@@ -220,6 +220,21 @@ __global__ void col_arg_combine_kernel(Stats st, int nch, int N, int BN, const i
 __global__ void filter_kernel(Stats st, int B, int M, int N, float th, int64_t* m0, int64_t* m1, float* s0, float* s1,
                               const int* Mb, const int* Nb) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (Mb && t < B * (M + N)) {
+    // a pair with an empty side (width pruning can empty one image of a ragged batch and keep the
+    // other): its rows have no argmax (arg0 = 0x7fffffff) and its columns' argmax names a dead row
+    // whose arg0 / max0 are stale -- no index is formed from either, the pair gets no matches
+    const int b = t < B * M ? t / M : (t - B * M) / N;
+    if (Mb[b] <= 0 || Nb[b] <= 0) {
+      if (t < B * M) {
+        if (t - b * M < Mb[b]) { m0[t] = -1; s0[t] = 0.f; }
+      } else {
+        const int u = t - B * M;
+        if (u - b * N < Nb[b]) { m1[u] = -1; s1[u] = 0.f; }
+      }
+      return;
+    }
+  }
   if (t < B * M) {
     const int b = t / M, i = t - b * M;
     if (Mb && i >= Mb[b]) return;

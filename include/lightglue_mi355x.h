@@ -401,6 +401,66 @@ int lg_plane_roundtrip(const float* x, int32_t R, int32_t K, int32_t lshift, int
                        int32_t* exponent, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Kernel-level checks of the assignment head (lightglue.py:284-296, 306-315, 321-337): the dual
+ * softmax and the mutual filter alone, on the caller's matching descriptors md0 [B][M][256] /
+ * md1 [B][N][256], matchability logits z0 [B][M] / z1 [B][N] and (nullable, device) per-pair counts.
+ * No handle, no weights.  Additive: the ABI version does not move.
+ * route:
+ *   LG_ASSIGN_MATERIALISED  sim = md0 md1^T by the bf16x6 GEMM, then the streaming assignment kernels:
+ *                           what lg_assignment_head and the pruned forward run.  With `sim` [B][M][N]
+ *                           given the GEMM is skipped (md0 / md1 may be null) and the kernels read it.
+ *   LG_ASSIGN_RECOMPUTED    the default eval route: md as the two-plane fp16 image the final_proj
+ *                           epilogue writes (one range slot, held to 2^4; rows_pad = B (M + N) rounded
+ *                           up to 256, plus 256), the similarity recomputed in two fp16x3 passes.  The
+ *                           image's exponent comes from the MEASURED max |md| (the forward predicts a
+ *                           bound from its weights instead, which is never smaller).  M % 16 == 0,
+ *                           N % 16 == 0; counts only with `fixed`.
+ * Counts (Mb, Nb [B], both or neither): clamped to [0, M] / [0, N]; an empty side empties the pair, as
+ * the forward does for a ragged batch.  fixed = 1: la keeps the [M+1][N+1] shape (real block, dustbin
+ * column at N, dustbin row at M, [M][N] = 0, everything else -inf); fixed = 0 (materialised only): la
+ * holds pair b's [Mb+1][Nb+1] block at the capacity strides and nothing else is written.  Outputs of
+ * rows >= Mb[b] / columns >= Nb[b] are never written.  raw_counts = 1 (counted materialised route
+ * only): the counts are clamped but a one-sided zero is kept -- what width pruning can leave; such a
+ * pair gets m = -1, s = 0 on its live side.  md rows past the counts must be finite (they are part
+ * of the measured maximum); nothing else of them reaches a result.
+ * poison: la / m0 / m1 / s0 / s1 are first filled with LG_ASSIGN_SENTINEL_F / _I; the plane-image rows
+ * past B (M + N) and, with counts, past each pair's counts are overwritten with fp16 NaN / Inf bit
+ * patterns before the launch (materialised from md with counts: the entries of sim outside each
+ * pair's block).  la is nullable.  Host outputs: exp_md, the exponent the planes were written with,
+ * and max_md (recomputed route; 0 otherwise).
+ * LG_E_INVALID (nothing launched, nothing written): a null required pointer, a non-positive size,
+ * B (M+1) (N+1) >= 2^31, Mb without Nb, fixed or raw_counts without counts, and on the recomputed
+ * route M % 16, N % 16, counts without fixed, a given sim.  LG_E_WORKSPACE: workspace smaller than
+ * lg_assign_workspace_bytes.  Synchronises the stream before returning. */
+enum { LG_ASSIGN_MATERIALISED = 0, LG_ASSIGN_RECOMPUTED = 1 };
+#define LG_ASSIGN_SENTINEL_F (-123.456f)
+#define LG_ASSIGN_SENTINEL_I (-77)
+typedef struct {
+  int32_t B, M, N;
+  const float* md0;
+  const float* md1;
+  const float* sim;             /* [B][M][N] or NULL */
+  const float* z0;
+  const float* z1;
+  const int32_t* Mb;            /* device [B] or NULL */
+  const int32_t* Nb;
+  int32_t fixed;
+  int32_t raw_counts;
+  float threshold;
+  int32_t route;                /* LG_ASSIGN_* */
+  int32_t poison;
+  float* la;                    /* [B][M+1][N+1] or NULL */
+  int64_t* m0;                  /* [B][M] */
+  int64_t* m1;                  /* [B][N] */
+  float* s0;
+  float* s1;
+  int32_t exp_md;               /* host out */
+  float max_md;                 /* host out */
+} lg_assign_args_t;
+int lg_assign_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes);
+int lg_assign(lg_assign_args_t* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training: the backward pass of LightGlue (the reference differentiates its forward with torch
  * autograd: gluefactory/train.py:436-450 over lightglue.py:444-579 and :614-663).  No reference
  * counterpart as an interface; these entry points are what a torch.autograd.Function binds.
