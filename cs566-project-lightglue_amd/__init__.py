@@ -32,4 +32,8 @@ def __getattr__(name):
         from . import assignment
 
         return getattr(assignment, name)
+    if name in ("eval_matches", "eval_matches_homography", "eval_matches_epipolar", "eval_homography_dlt"):
+        from . import match_eval
+
+        return getattr(match_eval, name)
     raise AttributeError(name)

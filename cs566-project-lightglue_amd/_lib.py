@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     # nearest-neighbour matcher (ABI 12, no handle)
     "lg_nn_workspace_bytes",
     "lg_nn_match",
+    # batched match evaluation (ABI 12, no handle)
+    "lg_eval_matches",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -444,6 +446,7 @@ def load():
             ctypes.c_int,
             [_P, _P, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double, i32] + [_P] * 9 + [sz, _P],
         ),
+        "lg_eval_matches": (ctypes.c_int, [_P] * 4 + [i32] * 3 + [_P] * 7 + [i32] + [_P] * 5),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_scratch_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),

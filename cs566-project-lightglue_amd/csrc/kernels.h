@@ -514,4 +514,19 @@ struct NnCall {
 size_t nn_workspace_bytes(int B, int M, int N, int D);
 hipError_t nn_match(const NnCall& c, void* workspace, hipStream_t st);
 
+// Batched match evaluation (match_eval.hip; eval/utils.py:40-91,176-196).  flags: 1 homography
+// precision, 2 epipolar precision, 4 weighted DLT; only what a set flag needs is read or written.
+struct EvalCall {
+  const float *kp0, *kp1;  // [B][M][2], [B][N][2]
+  const int64_t* m0;       // [B][M]
+  const float* s0;         // [B][M] (DLT weights)
+  int B, M, N, flags;
+  const int *num0, *num1;                // per-pair counts [B], or null
+  const float *H, *cam0, *cam1, *T;      // [B][9], [B][6], [B][6], [B][12]
+  const float* size0;                    // [B][2]
+  int *hom_counts, *epi_counts;          // [B][3] n, <1, <3;  [B][4] n, <1e-4, <5e-4, <1e-3
+  float *H_dlt, *H_err;                  // [B][9], [B]
+};
+hipError_t eval_matches(const EvalCall& c, hipStream_t st);
+
 }  // namespace lg

@@ -300,6 +300,38 @@ int lg_nn_match(const float* desc0, const float* desc1, int32_t B, int32_t M, in
                 float* similarity_or_null, float* log_assignment_or_null, int64_t* matches0, int64_t* matches1,
                 float* scores0, float* scores1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Batched match evaluation: what eval_matches_homography, eval_matches_epipolar and
+ * eval_homography_dlt (gluefactory/eval/utils.py:40-91,176-196) compute from a matcher's output, for
+ * every pair of a batch in one launch.  One more entry under ABI 12.  No handle, no workspace.
+ * Device inputs: kpts0 [B,M,2], kpts1 [B,N,2] fp32; matches0 [B,M] int64; scores0 [B,M] fp32 (the
+ * DLT's weights).  num0 / num1 (nullable, together): device int32 [B] per-pair counts of a ragged
+ * batch.  Match i of pair b is live when 0 <= matches0[b,i] < num1[b] (N without counts) and
+ * i < num0[b]; nothing else of a row is read, so padding may hold anything.
+ * flags selects the metrics; only what a set flag names is read or written:
+ *   LG_EVAL_HOMOGRAPHY  H_gt [B,9] -> hom_counts [B,3] int32: live matches, those with a symmetric
+ *                       transfer error (geometry/homography.py:314-323) below 1 px, below 3 px.  The
+ *                       inverse is the 3x3 adjugate inverse.
+ *   LG_EVAL_EPIPOLAR    cam0, cam1 [B,6] (w,h,fx,fy,cx,cy; no undistortion), T_0to1 [B,12] (R row-major,
+ *                       t) -> epi_counts [B,4] int32: live matches, those with a symmetric epipolar
+ *                       distance (geometry/epipolar.py:32-56, essential, not squared) below 1e-4,
+ *                       5e-4, 1e-3.
+ *   LG_EVAL_DLT         H_gt, scores0, image_size0 [B,2] (w,h) -> H_dlt [B,9] fp32, the score-weighted
+ *                       DLT homography (Hartley-normalised, smallest eigenvector of A^T W A by cyclic
+ *                       Jacobi, H[2,2] + 1e-8 = 1), and H_error_dlt [B] fp32, its mean corner error
+ *                       against H_gt.  Fewer than 4 live matches: H_dlt all +inf, the error NaN.
+ * All arithmetic is fp64 on the fp32 inputs; no atomics, identical results run to run.  Rows are
+ * indexed in 64 bits, so no int32 shape is too large.  Stream-ordered, asynchronous.
+ * LG_E_INVALID (checked before any device work): a null required pointer, a negative size, no or
+ * unknown flag bits, a set flag with one of its inputs or outputs null, one of num0 / num1 alone, a
+ * pointer off its natural alignment.  B == 0 or M == 0: LG_OK, nothing launched, no output written. */
+enum { LG_EVAL_HOMOGRAPHY = 1, LG_EVAL_EPIPOLAR = 2, LG_EVAL_DLT = 4 };
+int lg_eval_matches(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* scores0_or_null,
+                    int32_t B, int32_t M, int32_t N, const int32_t* num0_or_null, const int32_t* num1_or_null,
+                    const float* H_gt_or_null, const float* cam0_or_null, const float* cam1_or_null,
+                    const float* T_0to1_or_null, const float* image_size0_or_null, int32_t flags,
+                    int32_t* hom_counts_or_null, int32_t* epi_counts_or_null, float* H_dlt_or_null,
+                    float* H_error_dlt_or_null, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
