@@ -36,4 +36,8 @@ def __getattr__(name):
         from . import match_eval
 
         return getattr(match_eval, name)
+    if name in ("HomographyEstimator", "load_estimator", "eval_homography_robust", "ransac_homography"):
+        from . import robust
+
+        return getattr(robust, name)
     raise AttributeError(name)

@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = [
     "lg_nn_match",
     # batched match evaluation (ABI 12, no handle)
     "lg_eval_matches",
+    # batched robust homography estimation (ABI 12, no handle)
+    "lg_ransac_lds_matches",
+    "lg_ransac_homography",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -447,6 +450,11 @@ def load():
             [_P, _P, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double, i32] + [_P] * 9 + [sz, _P],
         ),
         "lg_eval_matches": (ctypes.c_int, [_P] * 4 + [i32] * 3 + [_P] * 7 + [i32] + [_P] * 5),
+        "lg_ransac_lds_matches": (i32, []),
+        "lg_ransac_homography": (
+            ctypes.c_int,
+            [_P] * 3 + [i32] * 3 + [_P] * 3 + [i32, ctypes.c_double, ctypes.c_uint64, ctypes.c_double] + [_P] * 8,
+        ),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_scratch_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),

@@ -529,4 +529,25 @@ struct EvalCall {
 };
 hipError_t eval_matches(const EvalCall& c, hipStream_t st);
 
+// Batched LO-RANSAC for homographies (ransac_homography.hip), one workgroup per pair.
+constexpr int RH_LDS_MATCHES = 2048;  // matches of a pair staged in LDS; more are read from m_kpts
+struct RansacCall {
+  const float *kp0, *kp1;  // [B][M][2], [B][N][2]
+  const int64_t* m0;       // [B][M], or null: slot i matches slot i
+  int B, M, N;
+  const int *num0, *num1;  // per-pair counts [B], or null
+  const float* th;         // [B] inlier thresholds in pixels
+  int max_iters;
+  double log_fail;         // log1p(-confidence)
+  uint64_t seed;
+  double min_area;
+  const float *H_gt, *size0;  // [B][9], [B][2], or null
+  float* H;                // [B][9]
+  uint8_t* inliers;        // [B][M]
+  int* info;               // [B][8]
+  float* m_kpts;           // [B][M][4]
+  float* H_err;            // [B], or null
+};
+hipError_t ransac_homography(const RansacCall& c, hipStream_t st);
+
 }  // namespace lg

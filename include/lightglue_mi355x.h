@@ -332,6 +332,43 @@ int lg_eval_matches(const float* kpts0, const float* kpts1, const int64_t* match
                     int32_t* hom_counts_or_null, int32_t* epi_counts_or_null, float* H_dlt_or_null,
                     float* H_error_dlt_or_null, void* stream);
 
+/* Batched robust homography estimation: a deterministic LO-RANSAC in place of the
+ * OpenCV / PoseLib estimators behind eval_homography_robust (gluefactory/eval/utils.py:132-173), for
+ * every pair of a batch in one launch.  One more entry under ABI 12.  No handle, no workspace.
+ * Device inputs: kpts0 [B,M,2], kpts1 [B,N,2] fp32; matches0 [B,M] int64, or null: M == N and slot i
+ * matches slot i (the estimator's m_kpts0 / m_kpts1 form).  num0 / num1 (nullable, together): device
+ * int32 [B] per-pair counts of a ragged batch.  Match i of pair b is live when i < num0[b] and
+ * 0 <= matches0[b,i] < num1[b] (M and N without counts); nothing else of a row is read.
+ * ransac_th [B] fp32: the inlier threshold of each pair in pixels (forward transfer error, r < th).
+ * Hypothesis t draws its four matches from splitmix64(splitmix64(seed) + (t << 16) + d), d = 0, 1, ...
+ * (repeats skipped, at most 64 draws), whatever the pair's place in the batch; a sample with a triple
+ * spanning less than min_area px^2 (twice the triangle's area) in either image, or with mixed
+ * orientations, is rejected.  Hypotheses run in rounds of 256 up to max_iters; after a round that
+ * raised the best minimal inlier count, 8 unweighted Hartley-normalised DLT refits (thresholds 3, 2.5,
+ * 2, 1.5, 1, 1, 1, 1 times th) polish it; the run stops when done * log1p(-(c/K)^4) <=
+ * log1p(-confidence) for the best polished count c >= 4 of K matches.
+ * Device outputs: H [B,9] fp32 (h33 = 1); inliers [B,M] uint8 in kpts0 slot order, the classification
+ * of every live match under the returned fp32 matrix (evaluated in fp64); info [B,8] int32: success,
+ * num_matches, num_inliers, best_t, best_minimal_count, rounds, valid_hypotheses, 0; m_kpts [B,M,4]
+ * fp32, 16-byte aligned: rows [0, num_matches) are the live matches (x0, y0, x1, y1) in slot order
+ * (get_matches_scores' points), the rest is not written; H_error [B] fp32 (nullable; needs H_gt [B,9]
+ * and image_size0 [B,2] (w,h)): the mean corner error against H_gt, +inf where success is 0.
+ * success is 0 with fewer than 4 matches, no valid hypothesis, fewer than 4 final inliers or a
+ * vanishing h33; H is then the identity and the mask all zero.
+ * All arithmetic is fp64; no atomics, identical results run to run.  Stream-ordered, asynchronous.
+ * LG_E_INVALID (checked before any device work): a null required pointer, a negative size, max_iters
+ * outside [1, 2^30], confidence outside (0, 1), a negative min_area, one of num0 / num1 alone, H_error
+ * without H_gt and image_size0, matches0 null with M != N, a pointer off its natural alignment.
+ * B == 0 or M == 0: LG_OK, nothing launched, no output written.
+ * lg_ransac_lds_matches: the number of matches of a pair the kernel keeps in LDS; pairs with more run
+ * the same arithmetic from m_kpts in global memory (same results, slower). */
+int32_t lg_ransac_lds_matches(void);
+int lg_ransac_homography(const float* kpts0, const float* kpts1, const int64_t* matches0_or_null, int32_t B, int32_t M,
+                         int32_t N, const int32_t* num0_or_null, const int32_t* num1_or_null, const float* ransac_th,
+                         int32_t max_iters, double confidence, uint64_t seed, double min_area,
+                         const float* H_gt_or_null, const float* image_size0_or_null, float* H, uint8_t* inliers,
+                         int32_t* info, float* m_kpts, float* H_error_or_null, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
