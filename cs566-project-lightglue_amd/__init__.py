@@ -40,4 +40,8 @@ def __getattr__(name):
         from . import robust
 
         return getattr(robust, name)
+    if name in ("RelativePoseEstimator", "eval_relative_pose_robust", "ransac_relpose"):
+        from . import relative_pose
+
+        return getattr(relative_pose, name)
     raise AttributeError(name)

@@ -55,6 +55,9 @@ EXPORTED_SYMBOLS = [
     # batched robust homography estimation (ABI 12, no handle)
     "lg_ransac_lds_matches",
     "lg_ransac_homography",
+    # batched robust relative pose and its five-point solver alone (ABI 12, no handle)
+    "lg_ransac_relpose",
+    "lg_essential_5pt",
     # training (backward pass)
     "lg_train_saved_bytes",
     "lg_train_saved_bytes_ex",
@@ -455,6 +458,11 @@ def load():
             ctypes.c_int,
             [_P] * 3 + [i32] * 3 + [_P] * 3 + [i32, ctypes.c_double, ctypes.c_uint64, ctypes.c_double] + [_P] * 8,
         ),
+        "lg_ransac_relpose": (
+            ctypes.c_int,
+            [_P] * 3 + [i32] * 3 + [_P] * 5 + [i32, ctypes.c_double, ctypes.c_uint64] + [_P] * 8,
+        ),
+        "lg_essential_5pt": (ctypes.c_int, [_P, i32, _P, _P, _P]),
         "lg_train_saved_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_saved_bytes_ex": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_train_scratch_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),

@@ -550,4 +550,29 @@ struct RansacCall {
 };
 hipError_t ransac_homography(const RansacCall& c, hipStream_t st);
 
+// Batched five-point LO-RANSAC for the relative pose (ransac_relpose.hip), one
+// workgroup per pair; matches are selected and staged as for RansacCall.
+struct RelposeCall {
+  const float *kp0, *kp1;    // [B][M][2], [B][N][2]
+  const int64_t* m0;         // [B][M], or null: slot i matches slot i
+  int B, M, N;
+  const int *num0, *num1;    // per-pair counts [B], or null
+  const float *cam0, *cam1;  // [B][4] fx, fy, cx, cy
+  const float* th;           // [B] inlier thresholds in pixels
+  int max_iters;
+  double log_fail;           // log1p(-confidence)
+  uint64_t seed;
+  const float* T_gt;         // [B][12] (R row-major, t), or null
+  float *R, *t;              // [B][9], [B][3]
+  uint8_t* inliers;          // [B][M]
+  int* info;                 // [B][8]
+  float* m_kpts;             // [B][M][4]
+  float* err;                // [B][3] t_err, r_err, their maximum; or null
+  double* ws;                // ransac_relpose_workspace_bytes(B): a round's candidates
+};
+size_t ransac_relpose_workspace_bytes(int B);
+hipError_t ransac_relpose(const RelposeCall& c, hipStream_t st);
+// the solver alone, one sample per thread: pts [S][5][4] normalised -> E [S][10][9], count [S]
+hipError_t essential_5pt(const float* pts, int S, double* E, int* count, hipStream_t st);
+
 }  // namespace lg

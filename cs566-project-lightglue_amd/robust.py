@@ -24,7 +24,9 @@ Differences from the reference:
   ``num_keypoints0/1`` for ragged batches, as ``match_eval`` does, and also returns ``M_0to1`` and
   ``inliers`` (in ``keypoints0`` slot order).
 * Inputs that are not on the device raise; there is no CPU path.
-* ``load_estimator("relative_pose", ...)`` raises: relative pose is out of scope.
+* ``load_estimator("relative_pose", ...)`` raises here: this module is the homography side.  Robust
+  relative pose lives in :mod:`lightglue_amd.relative_pose`, whose ``load_estimator``
+  resolves both types.
 """
 import ctypes
 

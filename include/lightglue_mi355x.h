@@ -369,6 +369,43 @@ int lg_ransac_homography(const float* kpts0, const float* kpts1, const int64_t* 
                          const float* H_gt_or_null, const float* image_size0_or_null, float* H, uint8_t* inliers,
                          int32_t* info, float* m_kpts, float* H_error_or_null, void* stream);
 
+/* Batched robust relative pose: a deterministic five-point LO-RANSAC in place of the
+ * OpenCV / PoseLib / pycolmap estimators behind eval_relative_pose_robust (gluefactory/eval/utils.py:
+ * 94-129), for every pair of a batch in one launch.  Two more entries under ABI 12.  No handle; the
+ * call makes and frees a stream-ordered allocation of 180 KiB per pair.
+ * kpts0, kpts1, matches0, num0 / num1, the live matches, their order, the sampler (five indices per
+ * sample), max_iters, confidence and seed are lg_ransac_homography's.  camera0, camera1 [B,4] fp32:
+ * fx, fy, cx, cy; a point is ((x - cx) / fx, (y - cy) / fy, 1), distortion is ignored.  ransac_th [B]
+ * fp32 in pixels: the kernel compares Sampson distances in normalised coordinates with th_n = th /
+ * mean(fx0, fy0, fx1, fy1).  Samples run in rounds of 256 up to max_iters: Nistér's five-point solver
+ * gives up to 10 essential matrices per sample and every one is scored against every match; after a
+ * round that raised the best minimal inlier count, 8 unweighted linear eight-point fits (thresholds 3,
+ * 2.5, 2, 1.5, 1, 1, 1, 1 times th_n), each projected onto the essential manifold, polish it; the run
+ * stops when done * log1p(-(c/K)^5) <= log1p(-confidence) for the best polished count c >= 5 of K.
+ * The kept matrix is decomposed and the (R, t) with the most inliers in front of both cameras wins.
+ * Device outputs: R [B,9], t [B,3] (unit norm) fp32; inliers [B,M] uint8 in kpts0 slot order: under
+ * E = [t]x R of those fp32 values, evaluated in fp64, "Sampson inlier and both depths positive";
+ * info [B,8] int32: success, num_matches, num_inliers, best_t, best_minimal_count, rounds,
+ * valid_samples, candidates_scored; m_kpts [B,M,4] fp32, 16-byte aligned, as lg_ransac_homography;
+ * errors [B,3] fp32 (nullable; needs T_gt [B,12], R row-major then t): t_err, r_err and their maximum
+ * in degrees (geometry/epipolar.py:127-155), +inf where success is 0.
+ * success is 0 with fewer than 5 matches, no candidate, fewer than 5 final inliers or no inlier in
+ * front of both cameras; R is then the identity, t zero and the mask all zero.
+ * All arithmetic is fp64; no atomics, identical results run to run.  Stream-ordered, asynchronous.
+ * LG_E_INVALID (checked before any device work): a null required pointer, a negative size, max_iters
+ * outside [1, 2^30], confidence outside (0, 1), one of num0 / num1 alone, errors without T_gt,
+ * matches0 null with M != N, a pointer off its natural alignment.
+ * B == 0 or M == 0: LG_OK, nothing launched, no output written.
+ * lg_essential_5pt (kernel-level entry, tests): the solver alone, one sample per thread.  pts [S,5,4]
+ * fp32 normalised (x0, y0, x1, y1); E [S,10,9] fp64: the sample's candidates (row-major, unit
+ * Frobenius norm, ascending z), count [S] int32 of them; nothing past count is written. */
+int lg_ransac_relpose(const float* kpts0, const float* kpts1, const int64_t* matches0_or_null, int32_t B, int32_t M,
+                      int32_t N, const int32_t* num0_or_null, const int32_t* num1_or_null, const float* camera0,
+                      const float* camera1, const float* ransac_th, int32_t max_iters, double confidence, uint64_t seed,
+                      const float* T_gt_or_null, float* R, float* t, uint8_t* inliers, int32_t* info, float* m_kpts,
+                      float* errors_or_null, void* stream);
+int lg_essential_5pt(const float* pts, int32_t S, double* E, int32_t* count, void* stream);
+
 /* Kernel-level entry (tests; the reference has no counterpart -- it is the SDPA call at
  * lightglue.py:139-149 in isolation): one launch of the forward's attention kernel.
  * q, k, v: fp32 head-major [B][H][Nq or Nk][64] device tensors, H * 64 == 256; ctx: fp32
