@@ -116,7 +116,10 @@ PRECISIONS = {"auto": 0, "bf16x6": 1}
 # flag on "auto" (LG_PREC_ATTN_F16): the eval forward's attention in half precision, conf "flash"
 PREC_ATTN_F16 = 0x100
 # lg_outputs_t.precision_used -> LightGlue.last_precision_used
-PRECISION_NAMES = {0: "fp16x3", 1: "bf16x6", PREC_ATTN_F16: "fp16x3+fp16attn"}
+# flag on "auto" (LG_PREC_GEMM_F16): the eval forward's trunk linears in half precision, conf "mp"
+PREC_GEMM_F16 = 0x400
+PRECISION_NAMES = {0: "fp16x3", 1: "bf16x6", PREC_ATTN_F16: "fp16x3+fp16attn", PREC_GEMM_F16: "fp16gemm",
+                   PREC_GEMM_F16 | PREC_ATTN_F16: "fp16gemm+fp16attn"}
 
 
 class LGConfig(ctypes.Structure):

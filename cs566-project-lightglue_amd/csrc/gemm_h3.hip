@@ -82,15 +82,22 @@ __device__ __forceinline__ void head_row_base_h3(const HeadLayout& hl, int row, 
 // ring and no barriers in the k-loop; the partial accumulators meet in LDS and wave 0 adds them
 // in wave order and runs the epilogue alone (small row counts: KS times the waves in flight per
 // tile, at the cost of a different rounding order from the KS = 1 kernels).
-template <int EPI, int BM, int NSTAGE, int BN = TB, int WN = 64, int KS = 1>
+//
+// H1 (GemmH3Args.h1, `mp: true`): the single-product numerics.  Each product is ONE
+// v_mfma_f32_16x16x32_f16 on the high planes, A_h . W_h; the stage holds [A h | W h] only
+// (h3_pipeline.h H1Stage), the low planes are neither copied nor read, and the accumulator is at
+// scale 2^(e1 - sw) (no 2^-11: the caller's acc_scale).  Everything after the k-loop is the
+// fp16x3 kernel's own code.  H1 = false compiles to the fp16x3 kernel, instruction for instruction.
+template <int EPI, int BM, int NSTAGE, int BN = TB, int WN = 64, int KS = 1, bool H1 = false>
 __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kernel(GemmH3Args g) {
   constexpr int WGN = BN / WN;               // waves along N
   constexpr int NW = (BM / 64) * WGN;        // waves of the tile (per k-split group)
   static_assert(KS == 1 || NW == 1, "split-k: single-wave tiles");
   constexpr int NJ = WN / 32;                // 32-column MFMA tiles per wave
   constexpr int BK = kKB;                    // k-tile = one k-block of the plane images (32)
-  using S = H3Stage<BM, BN, NW>;
+  using S = typename std::conditional<H1, H1Stage<BM, BN, NW>, H3Stage<BM, BN, NW>>::type;
   constexpr int APT = S::APT, WPT = S::WPT, STAGE_BYTES = S::STAGE_BYTES, PPW = S::PPW;
+  static_assert(!H1 || LG_GEMM_MF16, "H1: the 16x16x32 MFMA shape");
   constexpr int RING = NSTAGE * STAGE_BYTES;  // one k-split group's stages
   static_assert(KS == 1 || RING >= 64 * 64 * 4, "split-k: a partial accumulator fits the ring");
   __shared__ __attribute__((aligned(1024))) char smem[KS * RING];
@@ -137,6 +144,28 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
   // 1 KiB pieces [A h | A l | W h | W l]; wave w copies pieces PPW*w .. PPW*w + PPW-1.
   const uint32_t voff = lane * 16;
   auto issue = [&](int kt, int stage) {
+    if constexpr (H1) {
+      // [A h | W h]: plane 0 of each image; piece q = i * NW + wave (wave-uniform), q < PIECES
+      const bool first = kt < nk0;
+      const PlaneRef& A = first ? g.A0 : g.A1;
+      const int kbk = first ? kt : kt - nk0;
+      const char* asrc = reinterpret_cast<const char*>(A.p + ((size_t)kbk * A.rows_pad + m0) * BK);
+      const char* wsrc = reinterpret_cast<const char*>(g.W.p + ((size_t)kt * g.W.rows_pad + n0) * BK);
+#pragma unroll
+      for (int i = 0; i < PPW; ++i) {
+        const int q = i * NW + wave;
+        if ((i + 1) * NW > S::PIECES && q >= S::PIECES) break;
+        const bool isA = q < APT / 1024;
+        const char* src = isA ? asrc + q * 1024 : wsrc + (q - APT / 1024) * 1024;
+#if LG_GEMM_A_NT
+        if (g.stream && isA)
+          dma16_nt(src, voff, lds0 + stage * STAGE_BYTES + q * 1024);
+        else
+#endif
+          dma16(src, voff, lds0 + stage * STAGE_BYTES + q * 1024);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
       const int q = wave * PPW + i;  // wave-uniform
@@ -193,6 +222,21 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
 
   auto compute = [&](int stage) {
     const char* st = smem + ks * RING + stage * STAGE_BYTES;
+    if constexpr (H1) {
+      // one MFMA per 16 x 16 x 32 block: 4 + TJ fragment reads for 4 TJ MFMAs, no low pieces
+      const int c = lane >> 4, r16 = lane & 15;
+      f16x8 ah[TI];
+#pragma unroll
+      for (int i = 0; i < TI; ++i) ah[i] = h3_frag(st, 0, wm0 + i * 16 + r16, c);
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const f16x8 wh = h3_frag(st, APT, wn0 + j * 16 + r16, c);
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+          if constexpr (kMF16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], wh, acc[i][j], 0, 0, 0);
+      }
+      return;
+    }
     if constexpr (kMF16) {
       // h3_pipeline.h h3_mma_stage, kept in place: called as a function, the eight split-k kernels no
       // longer compile to the same code.  Lane: row (lane & 15) of each 16-row block, k chunk lane >> 4
@@ -258,7 +302,8 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
     if (kb + p < ke) issue(kb + p, p);
   for (int kt = kb; kt < ke; ++kt) {
     const int ahead = min(NSTAGE - 2, ke - 1 - kt);  // my k-tiles in flight beyond kt
-    ring_wait<NSTAGE, PPW>(ahead);
+    if constexpr (H1) h1_ring_wait<NSTAGE, S>(ahead, wave);
+    else ring_wait<NSTAGE, PPW>(ahead);
     lds_barrier<KS == 1>();  // split-k groups are single waves
     if (kt + NSTAGE - 1 < ke) issue(kt + NSTAGE - 1, (kt - kb + NSTAGE - 1) % NSTAGE);
     if (kt == nk0 && e0 != e1) scale_acc(ldexpf(1.f, e0 - e1));  // A0 -> A1 units (exact; rare)
@@ -715,22 +760,31 @@ __global__ __launch_bounds__((BM / 64) * (BN / WN) * 64 * KS) void gemm_h3_kerne
   }
 }
 
-template <int BM, int NSTAGE, int BN = TB, int WN = 64, int KS = 1>
+template <int BM, int NSTAGE, int BN = TB, int WN = 64, int KS = 1, bool H1 = false>
 hipError_t gemm_h3_launch(const GemmH3Args& a, int epi, hipStream_t st) {
   const int blocks = ((a.R + BM - 1) / BM) * (a.Nout / BN);
   const dim3 grid(blocks), block((BM / 64) * (BN / WN) * 64 * KS);
   switch (epi) {
-    case EPI_STORE: hipLaunchKernelGGL((gemm_h3_kernel<EPI_STORE, BM, NSTAGE, BN, WN, KS>), grid, block, 0, st, a); break;
-    case EPI_QKV_ROT: hipLaunchKernelGGL((gemm_h3_kernel<EPI_QKV_ROT, BM, NSTAGE, BN, WN, KS>), grid, block, 0, st, a); break;
+    case EPI_STORE: hipLaunchKernelGGL((gemm_h3_kernel<EPI_STORE, BM, NSTAGE, BN, WN, KS, H1>), grid, block, 0, st, a); break;
+    case EPI_QKV_ROT: hipLaunchKernelGGL((gemm_h3_kernel<EPI_QKV_ROT, BM, NSTAGE, BN, WN, KS, H1>), grid, block, 0, st, a); break;
     case EPI_CROSS_QKV:
-      hipLaunchKernelGGL((gemm_h3_kernel<EPI_CROSS_QKV, BM, NSTAGE, BN, WN, KS>), grid, block, 0, st, a);
+      hipLaunchKernelGGL((gemm_h3_kernel<EPI_CROSS_QKV, BM, NSTAGE, BN, WN, KS, H1>), grid, block, 0, st, a);
       break;
-    case EPI_PROBE: hipLaunchKernelGGL((gemm_h3_kernel<EPI_PROBE, BM, NSTAGE, BN, WN, KS>), grid, block, 0, st, a); break;
+    case EPI_PROBE: hipLaunchKernelGGL((gemm_h3_kernel<EPI_PROBE, BM, NSTAGE, BN, WN, KS, H1>), grid, block, 0, st, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
+#ifndef LG_GEMM_H1_STAGES
+// H1 kernels: ring depth.  An H1 stage is half an fp16x3 stage, so 4 stages (3 k-tiles in flight)
+// fill the LDS the fp16x3 kernels use with 2, and the epilogues' transpose buffers, sized by the
+// fp16x3 ring, still fit.  (The 64 x 64 tiles without k-split and with k-split 2 run 4 stages in
+// both numerics; their H1 rings are half the size.)  k-loop alone, 256 x 256 tiles, 131072 rows
+// (tools/kbench_gemm_h1.hip, DESIGN.md §5 "fp16 GEMMs"): 4 stages 55.7-63.0 / 65.1-68.5 / 34.6-36.5 us
+// for Wqkv / ffn.0 / ffn.3 against 58.3-73.2 / 70.9-74.5 / 38.4-40.8 with 2 (3: in between)
+#define LG_GEMM_H1_STAGES 4
+#endif
 #ifndef LG_GEMM_LN_WN
 #define LG_GEMM_LN_WN 64  // wave tile width: 64 -> 16 waves of 64 x 64, 128 -> 8 waves of 64 x 128
 #endif
@@ -739,6 +793,10 @@ hipError_t gemm_h3_launch(const GemmH3Args& a, int epi, hipStream_t st) {
 template <int WN, int BM = 128>
 hipError_t gemm_h3_ln_launch(const GemmH3Args& a, hipStream_t st) {
   const dim3 grid((a.R + BM - 1) / BM), block((BM / 64) * (512 / WN) * 64);
+  if (a.h1) {  // half-size stages: LG_GEMM_H1_STAGES of them in the fp16x3 kernel's LDS
+    hipLaunchKernelGGL((gemm_h3_kernel<EPI_LN_GELU, BM, LG_GEMM_H1_STAGES, 512, WN, 1, true>), grid, block, 0, st, a);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((gemm_h3_kernel<EPI_LN_GELU, BM, 2, 512, WN>), grid, block, 0, st, a);
   return hipGetLastError();
 }
@@ -794,6 +852,23 @@ static bool qkv_a_nt() {
   return v != 0;
 }
 
+// The H1 instantiations of gemm_h3's store / QKV routes: the same tile for the same shape and
+// overrides (gemm_tile_for, LG_GEMM_KSPLIT), LG_GEMM_H1_STAGES stages where fp16x3 runs 2
+static hipError_t gemm_h1_dispatch(const GemmH3Args& a, int epi, hipStream_t st) {
+  constexpr int NS = LG_GEMM_H1_STAGES;
+  switch (gemm_tile_for((long long)((a.R + TB - 1) / TB) * (a.Nout / TB))) {
+    case TILE_SMALL: {
+      int ksplit = 4;
+      if (const char* e = getenv("LG_GEMM_KSPLIT")) ksplit = atoi(e);
+      if (ksplit >= 4 && a.K >= 4 * kKB) return gemm_h3_launch<64, NS, 64, 64, 4, true>(a, epi, st);
+      if (ksplit >= 2 && a.K >= 2 * kKB) return gemm_h3_launch<64, 4, 64, 64, 2, true>(a, epi, st);
+      return gemm_h3_launch<64, 4, 64, 64, 1, true>(a, epi, st);
+    }
+    case TILE_MEDIUM: return gemm_h3_launch<128, NS, 128, 64, 1, true>(a, epi, st);
+    default: return gemm_h3_launch<256, NS, TB, 64, 1, true>(a, epi, st);
+  }
+}
+
 hipError_t gemm_h3(const GemmH3Args& a_in, int epi, hipStream_t st) {
   GemmH3Args a = a_in;
   a.stream = LG_GEMM_A_NT && (size_t)a.R * a.K * 4 >= nt_min_bytes();
@@ -808,6 +883,7 @@ hipError_t gemm_h3(const GemmH3Args& a_in, int epi, hipStream_t st) {
     if (use_small_tiles((a.R + 127) / 128)) return gemm_h3_ln_launch<64, 64>(a, st);
     return gemm_h3_ln_launch<LG_GEMM_LN_WN>(a, st);
   }
+  if (a.h1) return gemm_h1_dispatch(a, epi, st);
   switch (gemm_tile_for((long long)((a.R + TB - 1) / TB) * (a.Nout / TB))) {
     case TILE_SMALL: {
       // 64 x 64 single-wave tiles (fewer than 128 big tiles: at most 2048 of them), the k-tiles

@@ -73,6 +73,22 @@ struct H3Stage {
   static_assert(PIECES % NW == 0, "pieces per wave");
 };
 
+// The stage of the single-product fp16 GEMM (gemm_h3.hip, GemmH3Args.h1): the high planes only,
+// [A h | W h] -- half the bytes and half the LDS-DMA pieces of H3Stage.  The pieces are dealt to the
+// waves round-robin (piece q = i * NW + wave), so when NW does not divide PIECES (the LayerNorm
+// tiles: 40 pieces / 16 waves, 36 / 8) the first PIECES % NW waves copy PPW pieces per k-tile and
+// the others PPW - 1; each wave's counted wait uses its own count (h1_ring_wait).
+template <int BM, int BN, int NW>
+struct H1Stage {
+  static constexpr int APT = BM * kKB * 2;  // the A high-plane tile (bytes)
+  static constexpr int WPT = BN * kKB * 2;  // the W high-plane tile
+  static constexpr int STAGE_BYTES = APT + WPT;
+  static constexpr int PIECES = STAGE_BYTES / 1024;
+  static constexpr int PPW = (PIECES + NW - 1) / NW;
+  static constexpr bool EVEN = PIECES % NW == 0;
+  static constexpr int FULL = EVEN ? NW : PIECES % NW;  // waves that copy PPW pieces
+};
+
 // fragment (row r, 16-byte k-chunk c) of the plane tile at byte offset t0 of a stage (the chunk
 // swizzle of the plane images, common.h plane_swz)
 __device__ __forceinline__ f16x8 h3_frag(const char* st, int t0, int r, int c) {
@@ -87,6 +103,18 @@ __device__ __forceinline__ void ring_wait(int ahead) {
   if (NSTAGE >= 4 && ahead >= 2) dma_wait<2 * PPW>();
   else if (NSTAGE >= 3 && ahead >= 1) dma_wait<PPW>();
   else dma_wait<0>();
+}
+
+// ring_wait for an H1Stage: `wave` copies S::PPW pieces per k-tile if it is one of the first S::FULL
+// waves, S::PPW - 1 otherwise (wave-uniform branch; the counts are immediates)
+template <int NSTAGE, class S>
+__device__ __forceinline__ void h1_ring_wait(int ahead, int wave) {
+  if constexpr (S::EVEN) {
+    ring_wait<NSTAGE, S::PPW>(ahead);
+  } else {
+    if (wave < S::FULL) ring_wait<NSTAGE, S::PPW>(ahead);
+    else ring_wait<NSTAGE, S::PPW - 1>(ahead);
+  }
 }
 
 // The MFMA block of one k-tile: the wave's 64 x (16 TJ) tile, rows wm0.. of A and wn0.. of W in

@@ -126,7 +126,7 @@ hipError_t gemm_x6(const GemmArgs& a, int epi, int batch, hipStream_t st);
 
 // fp16x3 "linear" GEMM on plane images (common.h, gemm_h3.hip):
 //   Y = epilogue(A . W^T * acc_scale + bias), A = [A0 | A1] plane images, W = plane image of
-//   W * 2^sw (acc_scale = 2^-(11+sw)).  R rows (image rows_pad >= R, multiple of 256),
+//   W * 2^sw (acc_scale = 2^-(11+sw); with h1, 2^-sw).  R rows (image rows_pad >= R, multiple of 256),
 //   Nout a multiple of 256, K0 and K multiples of 32.
 struct PlaneRef {
   const _Float16* p;  // plane 0; plane 1 at p + ps
@@ -162,6 +162,8 @@ struct GemmH3Args {
   const float* ln_b;
   HeadLayout hl;      // EPI_QKV_ROT / EPI_CROSS_QKV (EPI_QKV_ROT with hl.cosb null: no rotary)
   int relu;           // EPI_STORE: max(., 0) after bias / scale / residual
+  int h1;             // single-product fp16 numerics: each product ONE fp16 MFMA on the high planes (plane 0
+                      // of A0 / A1 / W), the low planes not read; acc_scale = 2^-sw.  0: fp16x3
 };
 hipError_t gemm_h3(const GemmH3Args& a, int epi, hipStream_t st);
 // fp32 rows [R][K] (row stride ld) -> rows row0 .. row0+R-1 of a plane image (rows_pad), with

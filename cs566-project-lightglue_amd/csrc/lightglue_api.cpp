@@ -452,7 +452,9 @@ int lg_create(const lg_config_t* cfg, int device, lg_handle_t** out) {
   if (cfg->input_dim <= 0 || cfg->input_dim % 32) return fail(LG_E_INVALID, "input_dim must be a positive multiple of 32");
   if (cfg->precision == (LG_PREC_X6 | LG_PREC_ATTN_F16))
     return fail(LG_E_INVALID, "precision: LG_PREC_ATTN_F16 (fp16 attention) goes with LG_PREC_AUTO only, not with LG_PREC_X6");
-  if ((cfg->precision & ~LG_PREC_ATTN_F16) != LG_PREC_AUTO && cfg->precision != LG_PREC_X6)
+  if ((cfg->precision & ~LG_PREC_ATTN_F16) == (LG_PREC_X6 | LG_PREC_GEMM_F16))
+    return fail(LG_E_INVALID, "precision: LG_PREC_GEMM_F16 (fp16 GEMMs) goes with LG_PREC_AUTO only, not with LG_PREC_X6");
+  if ((cfg->precision & ~(LG_PREC_ATTN_F16 | LG_PREC_GEMM_F16)) != LG_PREC_AUTO && cfg->precision != LG_PREC_X6)
     return fail(LG_E_INVALID, "precision: unknown value " + std::to_string(cfg->precision));
   LG_HIP(hipSetDevice(device));
   lg_handle* h = new lg_handle();
@@ -726,7 +728,16 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
     h->prof_end(p, 2.0 * R * K * O * batch, 4.0 * (R * K + O * K + R * O) * batch, st);
     return e;
   };
-  auto gemmh = [&](const GemmH3Args& g, int epi) -> hipError_t {
+  // fp16 GEMMs (LG_PREC_GEMM_F16): input_proj and every trunk linear run the single-product kernel on
+  // the high planes, whose accumulator has no 2^11 (kernels.h GemmH3Args.h1); the assignment head's
+  // final_proj (trunk = false) stays fp16x3
+  const bool gemm_f16 = prec == PREC_H3 && (c.precision & LG_PREC_GEMM_F16);
+  auto gemmh = [&](const GemmH3Args& g_in, int epi, bool trunk = true) -> hipError_t {
+    GemmH3Args g = g_in;
+    if (gemm_f16 && trunk) {
+      g.h1 = 1;
+      g.acc_scale *= lg::kLoScale;  // exact: 2^-(11+sw) -> 2^-sw
+    }
     const int p = h->prof_begin(LG_KERNEL_GEMM, st);
     const hipError_t e = gemm_h3(g, epi, st);
     const double R = g.R, K = g.K, O = g.Nout;
@@ -744,7 +755,8 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
   auto attn = [&](const AttnSet& a0, const AttnSet& a1, float scale, bool cross, bool q_planes) -> hipError_t {
     const int p = h->prof_begin(LG_KERNEL_ATTENTION, st);
     // fp16 attention (LG_PREC_ATTN_F16) reads the fp16x3 forward's planes: everything else is PREC_H3
-    const int aprec = prec == PREC_H3 && (c.precision & LG_PREC_ATTN_F16) ? PREC_H1 : prec;
+    // fp16 GEMMs imply it: under autocast q, k and v are fp16 whatever `flash` says
+    const int aprec = prec == PREC_H3 && (c.precision & (LG_PREC_ATTN_F16 | LG_PREC_GEMM_F16)) ? PREC_H1 : prec;
     const hipError_t e = attention_f32(a0, a1, B, H, scale, aprec, st, w.apart, w.apart_floats, q_planes);
     // self: 2 matmuls per image (QK^T, PV); cross: one shared sim + two PV (lightglue.py:236-242)
     const double hd = 64.0 * H * B;
@@ -1068,7 +1080,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
       }
     }
   }
-  out->precision_used = prec == PREC_H3 ? (c.precision & LG_PREC_ATTN_F16) : LG_PREC_X6;
+  out->precision_used = prec == PREC_H3 ? (c.precision & (LG_PREC_ATTN_F16 | LG_PREC_GEMM_F16)) : LG_PREC_X6;
   if (slots_overflow) return fail(LG_E_INTERNAL, "range table exhausted (internal: range_slots undercounts)");
 
   // ---- assignment head of each pair's last executed layer (lightglue.py:549-551,
@@ -1094,7 +1106,7 @@ static int forward_pass(lg_handle_t* h, const lg_inputs_t* in, lg_outputs_t* out
         g.Yp = w.mdp; g.yps = (long long)md_rows_pad * D; g.yrows_pad = md_rows_pad;
         g.ro = RangeOut{rt, s_x, -1, 0.25f * h->gf[li], 0.f, 0.25f * h->bf_max[li], s_md, 0, 11};
       }
-      LG_HIP(gemmh(g, EPI_STORE));
+      LG_HIP(gemmh(g, EPI_STORE, false));  // final_proj: fp16x3 under every flag
     } else {
       GemmArgs g = gemm_base();
       g.A0 = w.X; g.lda0 = D; g.K0 = D; g.K = D; g.W = Wb + la.Wf; g.ldw = D; g.bias = Wb + la.bf;

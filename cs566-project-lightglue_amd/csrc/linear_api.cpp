@@ -105,7 +105,7 @@ const char* args_error(const lg_linear_args_t& a) {
   if (const char* e = shape_error(a.R, a.K0, a.K, a.Nout)) return e;
   if (!a.A0 || !a.W) return "null A0 / W";
   if (a.K0 < a.K && !a.A1) return "A1 is null with K0 < K";
-  if (a.precision != LG_PREC_AUTO && a.precision != LG_PREC_X6) return "bad precision";
+  if (a.precision != LG_PREC_AUTO && a.precision != LG_PREC_X6 && a.precision != LG_PREC_GEMM_F16) return "bad precision";
   if (a.lda0 < a.K0 || a.lda0 % 4 || (a.K0 < a.K && (a.lda1 < a.K - a.K0 || a.lda1 % 4))) return "bad lda";
   if (off16(a.A0) || off16(a.A1) || off16(a.W) || off16(a.bias) || off16(a.res) || off16(a.res2) || off16(a.Y) ||
       off16(a.Y2) || off16(a.yp) || off16(a.yp_rows) || off16(a.q) || off16(a.kp) || off16(a.vp) || off16(a.cosb) ||
@@ -121,7 +121,7 @@ const char* args_error(const lg_linear_args_t& a) {
   switch (a.epi) {
     case LG_LIN_STORE:
       if (!a.Y && !planes) return "no output requested";
-      if (planes && !a.yp && a.precision == LG_PREC_AUTO) return "want_planes without yp";
+      if (planes && !a.yp && a.precision != LG_PREC_X6) return "want_planes without yp";
       if (planes && !a.yp && !a.yp_rows) return "want_planes without yp / yp_rows";
       if ((a.res2 && !a.res) || (a.Y2 && !a.Y)) return "res2 / Y2 without res / Y";
       if (a.res && (a.ldr < a.Nout || a.ldr % 4)) return "bad ldr";
@@ -132,7 +132,7 @@ const char* args_error(const lg_linear_args_t& a) {
     case LG_LIN_LN_GELU:
       if (a.Nout != 512) return "LN + GELU needs Nout == 512";
       if (!a.ln_g || !a.ln_b) return "null ln_g / ln_b";
-      if (a.precision == LG_PREC_AUTO ? !a.yp : !a.yp_rows) return "null yp / yp_rows";
+      if (a.precision != LG_PREC_X6 ? !a.yp : !a.yp_rows) return "null yp / yp_rows";
       if (a.ln_route != 0 && a.ln_route != 1) return "bad ln_route";
       break;
     case LG_LIN_QKV_ROT:
@@ -345,7 +345,8 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
   g.K0 = K0; g.K = K;
   g.W = PlaneRef{wp, (long long)Nout * K, Nout};
   g.R = R; g.Nout = Nout;
-  g.acc_scale = std::ldexp(1.f, -(11 + sw));
+  g.h1 = a.precision == LG_PREC_GEMM_F16;  // one fp16 MFMA per product on the high planes: no 2^11
+  g.acc_scale = std::ldexp(1.f, g.h1 ? -sw : -(11 + sw));
   g.out_scale = 1.f;
   g.bias = a.bias;
   g.rtab = rtab; g.a0_slot = S_A0; g.a1_slot = K1 ? S_A1 : -1;

@@ -22,6 +22,14 @@ Deliberate behaviour differences from the reference:
   product is one fp16 MFMA, with fp32 accumulation and softmax statistics.  The context keeps its
   fp32 bits (the reference rounds its SDPA output to fp16).  The GEMMs and the assignment stay
   fp16x3; ``precision: "bf16x6"`` together with ``flash: true`` is rejected.
+* ``mp: true`` (the reference's autocast, :476) runs the eval forward's matrix-core linears --
+  ``input_proj``, ``Wqkv``, ``to_qk`` / ``to_v``, ``ffn.0`` (with ``out_proj`` / ``to_out`` folded in)
+  and ``ffn.3`` of every layer -- in half precision: activations and weights are rounded to fp16 once
+  and each product is one fp16 MFMA with fp32 accumulation.  The attention then runs as under
+  ``flash: true``, whatever ``flash`` says.  The residual stream, every epilogue, ``final_proj``, the
+  assignment and the pruning / early-stop decisions keep their fp32 bits (the reference rounds every
+  linear's output to fp16).  ``precision: "bf16x6"`` together with ``mp: true`` is rejected
+  (DESIGN.md §5 "fp16 GEMMs").
 * with pruning and B > 1, ``log_assignment`` and ``ref_descriptors*`` are per-pair LISTS (pair b's
   kept block; the reference asserts B == 1, :528,533); ``kept0/1`` and ``stop_layer`` give the
   per-pair counts.
@@ -129,7 +137,8 @@ def _ptr(t):
 
 # Extension keys (no reference counterpart).  "precision": matrix-core operand format of the HIP
 # kernels, both fp32-accurate -- "auto" (fp16x3, run-time operands range-scaled on the device) or "bf16x6"
-# (DESIGN.md §3); the reference's own "flash" key adds fp16 attention to "auto" (_lib.PREC_ATTN_F16).
+# (DESIGN.md §3); the reference's own "flash" key adds fp16 attention to "auto" (_lib.PREC_ATTN_F16), its
+# "mp" key fp16 GEMMs and fp16 attention (_lib.PREC_GEMM_F16).
 # "return_similarity": also return the final head's similarity md0 md1^T
 # [B, M, N] as pred["similarity"] (MatchAssignment's second output, lightglue.py:311,315; the input
 # of a Sinkhorn assignment head, configs[4]).
@@ -428,6 +437,11 @@ class LightGlue(nn.Module):
                 'lightglue_amd: "flash": true (fp16 attention) goes with "precision": "auto" only, not with '
                 '"precision": "bf16x6"'
             )
+        if bool(conf.mp) and str(conf.precision) == "bf16x6":
+            raise ValueError(
+                'lightglue_amd: "mp": true (fp16 GEMMs and attention) goes with "precision": "auto" only, not with '
+                '"precision": "bf16x6"'
+            )
         if conf.input_dim != conf.descriptor_dim:
             self.input_proj = nn.Linear(conf.input_dim, d, bias=True)
         else:
@@ -528,7 +542,9 @@ class LightGlue(nn.Module):
             float(c.width_confidence),
             float(c.filter_threshold),
             # the training entry points ignore the flag, so one handle serves train() and eval()
-            _lib.PRECISIONS[str(c.precision)] | (_lib.PREC_ATTN_F16 if bool(c.flash) else 0),
+            _lib.PRECISIONS[str(c.precision)]
+            | (_lib.PREC_ATTN_F16 if bool(c.flash) or bool(c.mp) else 0)
+            | (_lib.PREC_GEMM_F16 if bool(c.mp) else 0),
         )
 
     def _ensure_handle(self, device, upload=True):

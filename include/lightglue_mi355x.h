@@ -75,10 +75,20 @@ typedef struct {
                              * the probabilities rounded to fp16 once, one fp16 MFMA per product,
                              * fp32 accumulation and softmax statistics -- while the GEMMs and the
                              * assignment stay fp16x3.  Not fp32-accurate (DESIGN.md §5 "fp16
-                             * attention").  The training entry points ignore the flag. */
+                             * attention").  The training entry points ignore the flag.
+                             * LG_PREC_AUTO may also carry LG_PREC_GEMM_F16 (the reference's
+                             * `mp: true`, autocast): input_proj and every linear of the
+                             * transformer layers of lg_forward then form each product as one
+                             * fp16 MFMA on the high pieces of the same plane images -- operands
+                             * rounded to fp16 once, fp32 accumulation, epilogues and outputs
+                             * unchanged -- and the attention runs as under LG_PREC_ATTN_F16
+                             * (with or without that flag).  final_proj, the assignment and the
+                             * residual stream stay fp32-class.  Not fp32-accurate (DESIGN.md §5
+                             * "fp16 GEMMs").  The training entry points ignore the flag. */
 } lg_config_t;
 
-enum { LG_PREC_AUTO = 0, LG_PREC_X6 = 1, LG_PREC_ATTN_F16 = 0x100 }; /* the flag ORs with LG_PREC_AUTO only */
+/* the flags OR with LG_PREC_AUTO (and with each other) only */
+enum { LG_PREC_AUTO = 0, LG_PREC_X6 = 1, LG_PREC_ATTN_F16 = 0x100, LG_PREC_GEMM_F16 = 0x400 };
 
 typedef struct {
   int32_t B, M, N;              /* pairs, keypoints in image 0 / image 1 */
@@ -142,7 +152,8 @@ typedef struct {
   int32_t stop_layer;           /* host out: last executed layer (of pair 0) */
   int32_t kept0, kept1;         /* host out: M', N' of pair 0 after width pruning (= M, N without) */
   int32_t precision_used;       /* host out: 0 = fp16x3, 1 = bf16x6 (LG_PREC_X6), LG_PREC_ATTN_F16 =
-                                 * fp16x3 with fp16 attention */
+                                 * fp16x3 with fp16 attention; LG_PREC_GEMM_F16 (with or without
+                                 * LG_PREC_ATTN_F16, as configured) = fp16 GEMMs and fp16 attention */
   float* similarity;            /* device [B,M,N] or NULL: md0 md1^T of the final assignment head, the
                                  * second output of MatchAssignment.forward (lightglue.py:311,315;
                                  * the input of a Sinkhorn head, configs[4]); with pruning pair b's
@@ -470,7 +481,8 @@ typedef struct {
   int32_t res2_row0, ldr;
   float out_scale;
   int32_t relu;
-  int32_t precision;            /* LG_PREC_AUTO | LG_PREC_X6 */
+  int32_t precision;            /* LG_PREC_AUTO | LG_PREC_X6 | LG_PREC_GEMM_F16 (the fp16x3 preparation
+                                 * and outputs, each product one fp16 MFMA on the high planes) */
   int32_t epi;                  /* LG_LIN_* */
   int32_t ln_route;
   const float* ln_g;            /* [512] */
