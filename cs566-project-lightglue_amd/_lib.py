@@ -28,6 +28,12 @@ EXPORTED_SYMBOLS = [
     "lg_filter_matches",
     "lg_sinkhorn_workspace_bytes",
     "lg_log_optimal_transport",
+    # ragged batches (per-pair counts) for the Sinkhorn head, the filter and SuperGlue (ABI 12, additive)
+    "lg_filter_matches_ragged",
+    "lg_log_optimal_transport_ragged",
+    "lg_sinkhorn_rerun_count",
+    "lg_sinkhorn_force_exact",
+    "sg_forward_ragged",
     "lg_profile_enable",
     "lg_profile_read",
     "lg_attention_workspace_bytes",
@@ -426,6 +432,11 @@ def load():
         "lg_filter_matches": (ctypes.c_int, [_P, i32, i32, i32, ctypes.c_double, _P, _P, _P, _P, _P, sz, _P]),
         "lg_sinkhorn_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_log_optimal_transport": (ctypes.c_int, [_P, ctypes.c_float, i32, i32, i32, i32, _P, _P, sz, _P]),
+        "lg_filter_matches_ragged": (ctypes.c_int, [_P, i32, i32, i32, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, sz, _P]),
+        "lg_log_optimal_transport_ragged": (ctypes.c_int, [_P, ctypes.c_float, i32, i32, i32, _P, _P, i32, _P, _P, sz, _P]),
+        "lg_sinkhorn_rerun_count": (ctypes.c_int64, []),
+        "lg_sinkhorn_force_exact": (ctypes.c_int, [ctypes.c_int]),
+        "sg_forward_ragged": (ctypes.c_int, [_P, ctypes.POINTER(SGInputs), _P, _P, ctypes.POINTER(SGOutputs), _P, sz, _P]),
         "lg_profile_enable": (ctypes.c_int, [_P, ctypes.c_int]),
         "lg_attention_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_attention": (

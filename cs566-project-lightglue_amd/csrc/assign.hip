@@ -512,7 +512,8 @@ size_t assign_workspace_floats(int B, int M, int N) {
   auto r = [](size_t n) { return (n + 63) & ~size_t(63); };
   return 5 * r((size_t)B * M) + 5 * r((size_t)B * N) + 2 * r((size_t)B * nch * N) + 64;
 }
-size_t filter_workspace_floats(int B, int M, int N) { return assign_workspace_floats(B, M, N); }
+// + the clamped counts of a ragged call (lg_filter_matches_ragged), behind the argmax scratch
+size_t filter_workspace_floats(int B, int M, int N) { return assign_workspace_floats(B, M, N) + 2 * (size_t)B + 64; }
 
 template <bool FROM_LA>
 static hipError_t argmax_and_filter(const float* src, const Stats& s, const float* z0, float* la, int B, int M, int N,
@@ -633,10 +634,15 @@ hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const u
 }
 
 hipError_t filter_from_scores(const float* scores, int B, int M, int N, float th, float* ws, int64_t* m0, int64_t* m1,
-                              float* s0, float* s1, hipStream_t st) {
+                              float* s0, float* s1, hipStream_t st, const int* cnt) {
   if (B * M == 0 || B * N == 0) return hipErrorInvalidValue;
   const Stats s = carve(ws, B, M, N);
-  return argmax_and_filter<true>(scores, s, nullptr, nullptr, B, M, N, th, m0, m1, s0, s1, st);
+  if (!cnt) return argmax_and_filter<true>(scores, s, nullptr, nullptr, B, M, N, th, m0, m1, s0, s1, st);
+  // a ragged batch: the four-read kernels bound every loop by the pair's counts (the dustbin row /
+  // column of the fixed-shape scores are never read), then the padded points get -1 / 0
+  hipError_t e = argmax_and_filter<true>(scores, s, nullptr, nullptr, B, M, N, th, m0, m1, s0, s1, st, cnt, cnt + B);
+  if (e != hipSuccess) return e;
+  return ragged_pad_outputs(SegLayout{B, M, N}, cnt, m0, m1, s0, s1, nullptr, nullptr, st);
 }
 
 }  // namespace lg

@@ -381,6 +381,39 @@ __global__ void ragged_pad_outputs_kernel(SegLayout L, const int* cnt0, int64_t*
   }
 }
 
+__global__ void ragged_counts_kernel(SegLayout L, const int* n0, const int* n1, int* cnt) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= L.B) return;
+  int a = min(max(n0[t], 0), L.M0), b = min(max(n1[t], 0), L.N0);
+  if (a == 0 || b == 0) a = b = 0;  // an empty image: the pair has no matches, nothing of it runs
+  cnt[t] = a;
+  cnt[L.B + t] = b;
+}
+
+hipError_t ragged_counts(const SegLayout& L, const int* n0, const int* n1, int* cnt, hipStream_t st) {
+  if (L.B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ragged_counts_kernel, dim3((L.B + 255) / 256), dim3(256), 0, st, L, n0, n1, cnt);
+  return hipGetLastError();
+}
+
+__global__ void zero_dead_rows_kernel(float* x, int R, int K, int row0, RowMask rm) {
+  const int q = K / 4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)R * q; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / q), c = (int)(i % q) * 4;
+    if (row_live(rm, row0 + r)) continue;
+    *reinterpret_cast<f32x4*>(x + (size_t)r * K + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+hipError_t zero_dead_rows(float* x, int R, int K, int row0, const RowMask& rm, hipStream_t st) {
+  if (R <= 0 || !rm.cnt) return hipSuccess;
+  if (K % 4) return hipErrorInvalidValue;
+  const size_t n = (size_t)R * (K / 4);
+  hipLaunchKernelGGL(zero_dead_rows_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, st, x, R,
+                     K, row0, rm);
+  return hipGetLastError();
+}
+
 hipError_t ragged_pad_outputs(const SegLayout& L, const int* cnt0, int64_t* m0, int64_t* m1, float* s0, float* s1,
                               int64_t* prune0, int64_t* prune1, hipStream_t st) {
   const int R = L.B * (L.M0 + L.N0);

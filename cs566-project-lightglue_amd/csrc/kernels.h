@@ -290,8 +290,15 @@ hipError_t sim_row_stats(const SimH3Args& a, hipStream_t st);
 hipError_t sim_row_arg(const SimH3Args& a, const float* z0, float* max0, int* arg0, hipStream_t st);
 hipError_t assign_and_filter_h3(const AssignArgs& a, const PlaneRef& md, const unsigned* rtab, int slot, hipStream_t st);
 // filter_matches on an existing [B][M+1][N+1] log-assignment.
+// cnt (nullable; a ragged batch): clamped per-segment counts [2B] (SegLayout order: image 0 of every
+// pair, then image 1; ragged_counts) -- the argmaxes run over the pair's real block, padded points
+// get -1 / 0
 hipError_t filter_from_scores(const float* scores, int B, int M, int N, float th, float* ws, int64_t* m0, int64_t* m1,
-                              float* s0, float* s1, hipStream_t st);
+                              float* s0, float* s1, hipStream_t st, const int* cnt = nullptr);
+// cnt [2B] <- the caller's counts clamped to [0, capacity]; a pair with an empty image gets 0, 0
+hipError_t ragged_counts(const SegLayout& L, const int* n0, const int* n1, int* cnt, hipStream_t st);
+// zero the dead rows of x [R][K] (mask rows row0 + r): padding never leaves the library as stale bits
+hipError_t zero_dead_rows(float* x, int R, int K, int row0, const RowMask& rm, hipStream_t st);
 size_t filter_workspace_floats(int B, int M, int N);
 
 // Load-time fold of out_proj/to_out into ffn.0 (W1 [512][512], b1 [512], Wo [256][256], bo [256]);
@@ -360,8 +367,17 @@ hipError_t gemv_256_masked(const float* x, const float* w, const float* b, float
 
 // Sinkhorn (superglue.py:173-201).
 size_t sinkhorn_workspace_floats(int B, int M, int N);
+// num0 / num1 (both or neither; a ragged batch): per-pair counts [B] on the device, clamped there to
+// [0, M] / [0, N].  Pair b then gets what it gets alone at its own sizes, inside the fixed-shape Z:
+// real block at i < n0, j < n1, dustbin column at N, dustbin row at M, corner [M][N], the rest -inf;
+// a pair with an empty image is -inf except [M][N] = 0.  Padding of `scores` (NaN allowed) is unused.
 hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M, int N, int iters, float* Z, float* ws,
-                                 hipStream_t st);
+                                 hipStream_t st, const int* num0 = nullptr, const int* num1 = nullptr);
+// how often this process took the exact rerun after the scaled kernels flagged an underflow
+long long sinkhorn_exact_reruns();
+// test instrumentation: on != 0 skips the scaled kernels (N <= 4096 runs the exact running-max
+// kernels alone, without the flag read-back); returns the previous setting
+int sinkhorn_force_exact(int on);
 
 // ---- SuperPoint extractor (gluefactory_nonfree/superpoint.py, superpoint.hip) --------------
 // Feature maps are NHWC plane images: rows = pixels (n, y, x) in row-major order, K = channels.
@@ -460,6 +476,8 @@ struct SgEncArgs {
   int rows, n, nl;
   int ch[kSgMaxEnc + 1];
   SgEncLayer layer[kSgMaxEnc];
+  const int* cnt;       // [rows / n] or null: per-pair counts of a ragged batch -- padded points are
+                        // neither read nor written
 };
 hipError_t sg_keypoint_encoder(const SgEncArgs& a, hipStream_t st);
 hipError_t sg_transpose(const float* src, int rows, int cols, float* dst, hipStream_t st);

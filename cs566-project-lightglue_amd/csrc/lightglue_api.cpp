@@ -1391,6 +1391,22 @@ int lg_filter_matches(const float* scores, int32_t B, int32_t M, int32_t N, doub
   return LG_OK;
 }
 
+int lg_filter_matches_ragged(const float* scores, int32_t B, int32_t M, int32_t N, double threshold, const int32_t* num0,
+                             const int32_t* num1, int64_t* m0, int64_t* m1, float* s0, float* s1, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if ((num0 == nullptr) != (num1 == nullptr)) return fail(LG_E_INVALID, "num0 and num1 must be given together");
+  if (!num0) return lg_filter_matches(scores, B, M, N, threshold, m0, m1, s0, s1, workspace, workspace_bytes, stream);
+  if (!scores || !m0 || !m1 || !s0 || !s1) return fail(LG_E_INVALID, "null argument");
+  if (B <= 0 || M <= 0 || N <= 0) return fail(LG_E_INVALID, "max(): Expected reduction dim to have non-zero size");
+  if (!workspace || workspace_bytes < lg::filter_workspace_floats(B, M, N) * sizeof(float))
+    return fail(LG_E_WORKSPACE, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = reinterpret_cast<int*>((float*)workspace + lg::assign_workspace_floats(B, M, N));
+  LG_HIP(lg::ragged_counts(lg::SegLayout{B, M, N}, num0, num1, cnt, st));
+  LG_HIP(lg::filter_from_scores(scores, B, M, N, (float)threshold, (float*)workspace, m0, m1, s0, s1, st, cnt));
+  return LG_OK;
+}
+
 int lg_sinkhorn_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes) {
   if (!bytes) return fail(LG_E_INVALID, "null argument");
   *bytes = lg::sinkhorn_workspace_floats(B, M, N) * sizeof(float);
@@ -1406,6 +1422,22 @@ int lg_log_optimal_transport(const float* scores, float alpha, int32_t B, int32_
   LG_HIP(lg::log_optimal_transport(scores, alpha, B, M, N, iters, Z, (float*)workspace, (hipStream_t)stream));
   return LG_OK;
 }
+
+int lg_log_optimal_transport_ragged(const float* scores, float alpha, int32_t B, int32_t M, int32_t N, const int32_t* num0,
+                                    const int32_t* num1, int32_t iters, float* Z, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  if ((num0 == nullptr) != (num1 == nullptr)) return fail(LG_E_INVALID, "num0 and num1 must be given together");
+  if (!num0) return lg_log_optimal_transport(scores, alpha, B, M, N, iters, Z, workspace, workspace_bytes, stream);
+  if (!scores || !Z) return fail(LG_E_INVALID, "null argument");
+  if (B < 0 || M < 1 || N < 1 || iters < 0) return fail(LG_E_INVALID, "bad shape (a ragged batch needs capacities >= 1)");
+  if (!workspace || workspace_bytes < lg::sinkhorn_workspace_floats(B, M, N) * sizeof(float))
+    return fail(LG_E_WORKSPACE, "workspace too small");
+  LG_HIP(lg::log_optimal_transport(scores, alpha, B, M, N, iters, Z, (float*)workspace, (hipStream_t)stream, num0, num1));
+  return LG_OK;
+}
+
+int64_t lg_sinkhorn_rerun_count(void) { return (int64_t)lg::sinkhorn_exact_reruns(); }
+int lg_sinkhorn_force_exact(int on) { return lg::sinkhorn_force_exact(on); }
 
 namespace {
 size_t attention_ws(int B, int H, int Nq, int Nk, size_t& kv_off, size_t& img_off, int& rp, size_t* part_off = nullptr) {

@@ -16,7 +16,10 @@
 // HBM bound: B*M*N*4 bytes read per iteration (+ partials, ~3%).
 // General path (N > 4096): the u-step walks rows of `scores`, the v-step walks rows of a
 // transposed copy made once (tiled LDS transpose); one wave per row, two-pass max-then-sum.
+// Ragged batches (per-pair row / column counts): separate RAGGED instantiations of every kernel,
+// see SkPair below; the uniform instantiations are the code they were without it.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
 
@@ -33,10 +36,50 @@
 
 namespace lg {
 
-__global__ __launch_bounds__(256) void transpose_kernel(const float* src, float* dst, int M, int N) {
+// A ragged batch (per-pair counts): pair b has m <= M real rows and n <= N real
+// columns, stored first; the rest of its [M][N] slot is arbitrary (NaN allowed) and is never used.
+// sk_pairs_kernel clamps the caller's counts on the device and derives the pair's own marginals
+// (superglue.py:194-197 at the pair's sizes); every kernel below has a RAGGED instantiation that
+// reads its pair's entry once, bounds its row / column loops by the counts, and addresses the
+// dustbin row / column at the capacity index (u[M], v[N], Z[M][.], Z[.][N]).  The uniform
+// instantiations (RAGGED = false) never touch the table.
+struct SkPair {
+  int m, n;                   // clamped counts; both 0 for a pair with an empty image
+  float norm, mu_bin, nu_bin; // -log(m+n), log n + norm (dustbin row), log m + norm (dustbin column)
+  int pad[3];
+};
+
+// A pair whose counts equal the capacities takes the host's constants (the uniform launch's own
+// bits); an empty pair (either count 0: superglue.py:257-264) gets zeros -- nothing of it is used.
+__global__ void sk_pairs_kernel(const int* n0, const int* n1, SkPair* pairs, int B, int M, int N, float norm, float mu_bin,
+                                float nu_bin) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B) return;
+  int a = min(max(n0[t], 0), M), c = min(max(n1[t], 0), N);
+  SkPair p{};
+  if (a == 0 || c == 0) {
+    a = c = 0;
+  } else if (a == M && c == N) {
+    p.norm = norm; p.mu_bin = mu_bin; p.nu_bin = nu_bin;
+  } else {
+    const float ms = (float)a, ns = (float)c;
+    p.norm = -logf(ms + ns);
+    p.mu_bin = logf(ns) + p.norm;
+    p.nu_bin = logf(ms) + p.norm;
+  }
+  p.m = a; p.n = c;
+  pairs[t] = p;
+}
+
+template <bool RAGGED = false>
+__global__ __launch_bounds__(256) void transpose_kernel(const float* src, float* dst, int M, int N,
+                                                        const SkPair* pairs = nullptr) {
   __shared__ float tile[64][65];
   const int b = blockIdx.z;
   const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+  if constexpr (RAGGED) {  // a tile wholly in the padding: never read back
+    if (i0 >= pairs[b].m || j0 >= pairs[b].n) return;
+  }
   const float* s = src + (size_t)b * M * N;
   float* d = dst + (size_t)b * M * N;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -53,8 +96,12 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* src, float*
 
 // One Sinkhorn half-step over `rows`+1 rows of length `cols`+1 (last row / column = dustbin).
 // src: [B][rows][cols] real scores; other: the opposite potential [B][cols+1]; out: [B][rows+1].
+// RAGGED: the pair's own row / column counts bound the walk (swapped: src is the transposed copy,
+// rows are the pair's columns); position nc of the walk is the dustbin, read at index cols.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(256) void lse_step_kernel(const float* src, const float* other, float* out, int B, int rows,
-                                                       int cols, float alpha, float lm_in, float lm_bin) {
+                                                       int cols, float alpha, float lm_in, float lm_bin,
+                                                       const SkPair* pairs = nullptr, int swapped = 0) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= B * (rows + 1)) return;
@@ -62,16 +109,25 @@ __global__ __launch_bounds__(256) void lse_step_kernel(const float* src, const f
   const float* o = other + (size_t)b * (cols + 1);
   const float* x = src + ((size_t)b * rows + i) * cols;
   const bool bin_row = i == rows;
+  int nc = cols;
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    const int nr = swapped ? pr.n : pr.m;
+    nc = swapped ? pr.m : pr.n;
+    if (i >= nr && !bin_row) return;  // a padded row: no potential
+    lm_in = pr.norm;
+    lm_bin = swapped ? pr.nu_bin : pr.mu_bin;
+  }
   float m = -INFINITY;
-  for (int j = lane; j <= cols; j += 64) {
-    const float z = (bin_row || j == cols) ? alpha : x[j];
-    m = fmaxf(m, z + o[j]);
+  for (int j = lane; j <= nc; j += 64) {
+    const float z = (bin_row || j == nc) ? alpha : x[j];
+    m = fmaxf(m, z + o[j == nc ? cols : j]);
   }
   m = wave_max(m);
   float s = 0.f;
-  for (int j = lane; j <= cols; j += 64) {
-    const float z = (bin_row || j == cols) ? alpha : x[j];
-    s += expf((z + o[j]) - m);
+  for (int j = lane; j <= nc; j += 64) {
+    const float z = (bin_row || j == nc) ? alpha : x[j];
+    s += expf((z + o[j == nc ? cols : j]) - m);
   }
   s = wave_sum(s);
   if (lane == 0) {
@@ -83,10 +139,20 @@ __global__ __launch_bounds__(256) void lse_step_kernel(const float* src, const f
 // out = Zc + u_i + v_j - norm (superglue.py:199-201): one row per blockIdx.x, 1024 columns per
 // blockIdx.y; each load / store instruction covers 256 consecutive columns (coalesced whatever
 // the alignment of the N+1-long output rows)
+// RAGGED: also the frame of the fixed-shape Z -- real block at i < m, j < n, dustbin column at N
+// (i < m), dustbin row at M (j < n), the corner [M][N]; every other entry -inf.  An empty pair:
+// -inf except [M][N] = 0.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(256) void sinkhorn_out_kernel(const float* scores, const float* u, const float* v,
-                                                           float* Z, int M, int N, float alpha, float norm) {
+                                                           float* Z, int M, int N, float alpha, float norm,
+                                                           const SkPair* pairs = nullptr) {
   const int r = blockIdx.x;  // b * (M + 1) + i
   const int b = r / (M + 1), i = r - b * (M + 1);
+  int mr = M, nr = N;
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    mr = pr.m; nr = pr.n; norm = pr.norm;
+  }
   const float ui = u[r];
   const float* vb = v + (size_t)b * (N + 1);
   const float* sr = scores + ((size_t)b * M + min(i, M - 1)) * N;
@@ -95,12 +161,20 @@ __global__ __launch_bounds__(256) void sinkhorn_out_kernel(const float* scores, 
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int j = blockIdx.y * 1024 + e * 256 + threadIdx.x;
-    x[e] = (i < M && j < N) ? sr[j] : alpha;
+    x[e] = (i < mr && j < nr) ? sr[j] : alpha;
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int j = blockIdx.y * 1024 + e * 256 + threadIdx.x;
-    if (j <= N) zr[j] = ((x[e] + ui) + vb[j]) - norm;
+    if constexpr (RAGGED) {
+      if (j <= N) {
+        const bool in = (i < mr || i == M) && (j < nr || j == N);  // empty pair (mr = nr = 0): only [M][N]
+        const float z = mr == 0 ? 0.f : ((x[e] + ui) + vb[j]) - norm;
+        zr[j] = in ? z : -INFINITY;
+      }
+    } else {
+      if (j <= N) zr[j] = ((x[e] + ui) + vb[j]) - norm;
+    }
   }
 }
 
@@ -148,19 +222,35 @@ __device__ __forceinline__ void lse_merge(float& am, float& as, float bm, float 
 // One iteration: u <- log_mu - LSE_j(Zc + v) for the workgroup's rows, then this workgroup's
 // column partials of Zc + u.  K4 = float4 column chunks per lane (columns 256k + 4 lane + e);
 // VEC: rows are 16-byte aligned (N % 4 == 0).
-template <int K4, bool VEC, int W, bool PF = false>
+// RAGGED (PF = false only): Mr / Nr are the pair's counts -- columns >= Nr are masked like the
+// columns >= N of the uniform kernel, rows in [Mr, M) are skipped, the dustbin row stays row M.  A
+// workgroup whose rows are all padding writes neutral partials (-inf, 0) and leaves.
+template <int K4, bool VEC, int W, bool PF = false, bool RAGGED = false>
 __global__ __launch_bounds__(W * 64) void sinkhorn_fused_kernel(const float* __restrict__ scores,
                                                                        const float* __restrict__ v, float* u,
                                                                        float2* part, int M, int N, int rw, int P,
-                                                                       float alpha, float lm_in, float lm_bin) {
+                                                                       float alpha, float lm_in, float lm_bin,
+                                                                       const SkPair* pairs = nullptr) {
+  static_assert(!(PF && RAGGED), "the ragged walk loads each row at the top of its iteration");
   __shared__ float2 mbuf[W / 2][kSkMaxN + 1]; // wave-pair merge buffers
   __shared__ float4 vs[kSkMaxN / 4 + 1];      // v of the real columns
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / P, p = blockIdx.x - b * P;
+  int Mr = M, Nr = N;
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    Mr = pr.m; Nr = pr.n; lm_in = pr.norm; lm_bin = pr.mu_bin;
+    const int rb0 = p * W * rw;  // the workgroup's row run [rb0, rb0 + W rw)
+    if (rb0 >= Mr && !(rb0 <= M && M < rb0 + W * rw)) {
+      float2* dst = part + ((size_t)b * P + p) * (N + 1);
+      for (int c = tid; c <= N; c += W * 64) dst[c] = make_float2(-INFINITY, 0.f);
+      return;
+    }
+  }
   const float* vb = v + (size_t)b * (N + 1);
   for (int j = tid; j < 4 * (kSkMaxN / 4 + 1); j += W * 64)  // finite past N: masked columns stay -inf
-    reinterpret_cast<float*>(vs)[j] = j < N ? vb[j] : 0.f;
+    reinterpret_cast<float*>(vs)[j] = j < Nr ? vb[j] : 0.f;
   const float vbin = vb[N];
   __syncthreads();
 
@@ -182,21 +272,25 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_fused_kernel(const float* __r
       const int c = 256 * k + 4 * lane;
       if (bin_row) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x[k][e] = c + e < N ? alpha : -INFINITY;
+        for (int e = 0; e < 4; ++e) x[k][e] = c + e < Nr ? alpha : -INFINITY;
       } else if (VEC) {
-        const f32x4 t = c < N ? *reinterpret_cast<const f32x4*>(row + c) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        const f32x4 t = c < Nr ? *reinterpret_cast<const f32x4*>(row + c) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x[k][e] = t[e];
+        for (int e = 0; e < 4; ++e) x[k][e] = RAGGED && c + e >= Nr ? -INFINITY : t[e];  // Nr need not be a multiple of 4
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x[k][e] = c + e < N ? row[c + e] : -INFINITY;
+        for (int e = 0; e < 4; ++e) x[k][e] = c + e < Nr ? row[c + e] : -INFINITY;
       }
     }
   };
   float x[K4][4];
-  if (r0 < r1) load_row(r0, x);
+  if (!RAGGED && r0 < r1) load_row(r0, x);
 #pragma unroll 1
   for (int i = r0; i < r1; ++i) {
+    if constexpr (RAGGED) {
+      if (i >= Mr && i != M) continue;  // padding
+      load_row(i, x);
+    }
     // PF: next row in flight while this one is reduced (measured slower: 10.9 vs 9.3 ms at
     // configs[4] -- the kernel is VALU-bound and the row copy costs 64 moves)
     float xn[K4][4];
@@ -252,7 +346,7 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_fused_kernel(const float* __r
     } else {
       bs += tb;
     }
-    if (i + 1 < r1) {
+    if (!RAGGED && i + 1 < r1) {
       if constexpr (PF) {
 #pragma unroll
         for (int k = 0; k < K4; ++k)
@@ -310,10 +404,18 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_fused_kernel(const float* __r
 }
 
 // v_j = log_nu_j - LSE_i(Zc_ij + u_i) from the P workgroup partials of column j
-__global__ void sinkhorn_colmerge_kernel(const float2* part, float* v, int B, int N, int P, float lm_in, float lm_bin) {
+// RAGGED: a padded column (j in [n, N)) has no potential and is left alone
+template <bool RAGGED = false>
+__global__ void sinkhorn_colmerge_kernel(const float2* part, float* v, int B, int N, int P, float lm_in, float lm_bin,
+                                         const SkPair* pairs = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= B * (N + 1)) return;
   const int b = t / (N + 1), j = t - b * (N + 1);
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    if (j >= pr.n && j != N) return;
+    lm_in = pr.norm; lm_bin = pr.nu_bin;
+  }
   const float2* q = part + (size_t)b * P * (N + 1) + j;
   float m = -INFINITY, s = 0.f;
   for (int p = 0; p < P; ++p) {
@@ -333,22 +435,35 @@ __global__ void sinkhorn_colmerge_kernel(const float2* part, float* v, int B, in
 // LSE_i(Zc_ij + u_i) = log S_j - v_j.  Terms below fp32's range are lost where the exact kernel
 // keeps them; the merge flags any column whose S_j falls under 2^-100 and
 // log_optimal_transport then reruns with sinkhorn_fused_kernel (running max per column).
-template <int K4, bool VEC, int W, bool NT>
+// RAGGED: as in sinkhorn_fused_kernel -- columns >= Nr masked (their sums stay 0), real rows end at
+// Mr, the dustbin row stays row M; a workgroup of padding rows writes zero partials and leaves.
+template <int K4, bool VEC, int W, bool NT, bool RAGGED = false>
 __global__ __launch_bounds__(W * 64) void sinkhorn_scaled_kernel(const float* __restrict__ scores,
                                                                  const float* __restrict__ v, float* u, float* part,
                                                                  int M, int N, int rw, int P, float alpha, float lm_in,
-                                                                 float lm_bin) {
+                                                                 float lm_bin, const SkPair* pairs = nullptr) {
   __shared__ float sbuf[W / 2][kSkMaxN + 1];  // wave-pair merge buffers
   __shared__ float4 vs[kSkMaxN / 4 + 1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / P, p = blockIdx.x - b * P;
+  int Mr = M, Nr = N;
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    Mr = pr.m; Nr = pr.n; lm_in = pr.norm; lm_bin = pr.mu_bin;
+    const int rb0 = p * W * rw;  // the workgroup's row run [rb0, rb0 + W rw)
+    if (rb0 >= Mr && !(rb0 <= M && M < rb0 + W * rw)) {
+      float* dst = part + ((size_t)b * P + p) * (N + 1);
+      for (int c = tid; c <= N; c += W * 64) dst[c] = 0.f;
+      return;
+    }
+  }
   const float* vb = v + (size_t)b * (N + 1);
   // LG_SK_LOG2: the row pass works in log2 units (v staged as v log2 e, scores scaled by the same
   // FMA that adds v), so the exponentials are bare v_exp_f32 with no per-score multiply, and the
   // adds / FMAs run two columns per packed instruction
   constexpr float vsc = LG_SK_LOG2 ? 1.4426950408889634f : 1.f;
-  for (int j = tid; j < 4 * (kSkMaxN / 4 + 1); j += W * 64) reinterpret_cast<float*>(vs)[j] = j < N ? vb[j] * vsc : 0.f;
+  for (int j = tid; j < 4 * (kSkMaxN / 4 + 1); j += W * 64) reinterpret_cast<float*>(vs)[j] = j < Nr ? vb[j] * vsc : 0.f;
   const float vbin = vb[N];
   const float ybin = LG_SK_LOG2 ? (alpha + vbin) * vsc : alpha + vbin;
   __syncthreads();
@@ -444,7 +559,7 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_scaled_kernel(const float* __
     accb = fmaf(eb, a, accb);
 #endif
   };
-  const int rl = min(r1, M);  // real rows; the dustbin row M (all alpha) is handled after
+  const int rl = min(r1, Mr);  // real rows; the dustbin row M (all alpha) is handled after
   auto load = [&](float (&y)[K4][4], int i) {
     const char* row = reinterpret_cast<const char*>(scores + ((size_t)b * M + i) * N);
 #pragma unroll
@@ -453,16 +568,16 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_scaled_kernel(const float* __
       if (VEC) {
         f32x4 t = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         if (NT) {
-          if (c < N) t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + 1024 * k + (uint32_t)(16 * lane)));
+          if (c < Nr) t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + 1024 * k + (uint32_t)(16 * lane)));
         } else {
-          if (c < N) t = *reinterpret_cast<const f32x4*>(row + 1024 * k + (uint32_t)(16 * lane));
+          if (c < Nr) t = *reinterpret_cast<const f32x4*>(row + 1024 * k + (uint32_t)(16 * lane));
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[k][e] = t[e];
+        for (int e = 0; e < 4; ++e) y[k][e] = RAGGED && c + e >= Nr ? -INFINITY : t[e];  // Nr need not be a multiple of 4
       } else {
         const float* rf = reinterpret_cast<const float*>(row);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[k][e] = c + e < N ? rf[c + e] : -INFINITY;
+        for (int e = 0; e < 4; ++e) y[k][e] = c + e < Nr ? rf[c + e] : -INFINITY;
       }
     }
   };
@@ -482,7 +597,7 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_scaled_kernel(const float* __
 #pragma unroll
     for (int k = 0; k < K4; ++k)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) y[k][e] = 256 * k + 4 * lane + e < N ? alpha : -INFINITY;
+      for (int e = 0; e < 4; ++e) y[k][e] = 256 * k + 4 * lane + e < Nr ? alpha : -INFINITY;
     process(y, M, true);
   }
 
@@ -537,11 +652,23 @@ __global__ __launch_bounds__(W * 64) void sinkhorn_scaled_kernel(const float* __
 }
 
 // v_j <- log_nu_j - (log S_j - v_j), S_j = sum of the P partials; flags S_j < 2^-100
+// RAGGED: a padded column (j in [n, N)) has an empty sum -- it is not merged and cannot raise the
+// flag; neither can any column of an empty pair
+template <bool RAGGED = false>
 __global__ void sinkhorn_scaled_merge_kernel(const float* part, float* v, int* flag, int B, int N, int P, float lm_in,
-                                             float lm_bin) {
+                                             float lm_bin, const SkPair* pairs = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   bool low = false;
-  if (t < B * (N + 1)) {
+  bool on = t < B * (N + 1);
+  if constexpr (RAGGED) {
+    if (on) {
+      const SkPair pr = pairs[t / (N + 1)];
+      const int j = t % (N + 1);
+      on = pr.m > 0 && (j < pr.n || j == N);
+      lm_in = pr.norm; lm_bin = pr.nu_bin;
+    }
+  }
+  if (on) {
     const int b = t / (N + 1), j = t - b * (N + 1);
     const float* q = part + (size_t)b * P * (N + 1) + j;
     float S = 0.f;
@@ -558,14 +685,21 @@ __global__ void sinkhorn_scaled_merge_kernel(const float* part, float* v, int* f
 // partials w, w + WAYS, ..., then the ways are added in order): a pair group of one or two pairs
 // has P = 128-256 partials per column, whose sequential sum in one thread was latency-bound
 // (one 4097-thread launch, 256 dependent-latency loads each).  grid (ceil((N+1)/64), B), block (64, WAYS).
-template <int WAYS>
+template <int WAYS, bool RAGGED = false>
 __global__ __launch_bounds__(64 * WAYS) void sinkhorn_scaled_merge_ways_kernel(const float* part, float* v, int* flag, int N,
-                                                                               int P, float lm_in, float lm_bin) {
+                                                                               int P, float lm_in, float lm_bin,
+                                                                               const SkPair* pairs = nullptr) {
   __shared__ float red[WAYS][64];
   const int tx = threadIdx.x, w = threadIdx.y;
   const int b = blockIdx.y, j = blockIdx.x * 64 + tx;
+  bool on = j <= N;
+  if constexpr (RAGGED) {
+    const SkPair pr = pairs[b];
+    on = on && pr.m > 0 && (j < pr.n || j == N);
+    lm_in = pr.norm; lm_bin = pr.nu_bin;
+  }
   float S = 0.f;
-  if (j <= N) {
+  if (on) {
     const float* q = part + (size_t)b * P * (N + 1) + j;
 #pragma unroll 4
     for (int p = w; p < P; p += WAYS) S += q[(size_t)p * (N + 1)];
@@ -577,7 +711,7 @@ __global__ __launch_bounds__(64 * WAYS) void sinkhorn_scaled_merge_ways_kernel(c
 #pragma unroll
   for (int k = 0; k < WAYS; ++k) S += red[k][tx];
   bool low = false;
-  if (j <= N) {
+  if (on) {
     const size_t t = (size_t)b * (N + 1) + j;
     low = !(S >= 0x1p-100f);
     const float lse = logf(S) - v[t];
@@ -587,47 +721,76 @@ __global__ __launch_bounds__(64 * WAYS) void sinkhorn_scaled_merge_ways_kernel(c
 }
 
 static void launch_scaled_merge(const float* part, float* v, int* flag, int B, int N, int P, float lm_in, float lm_bin,
-                                hipStream_t st) {
-  if (P >= 64) {
-    hipLaunchKernelGGL(sinkhorn_scaled_merge_ways_kernel<8>, dim3((N + 1 + 63) / 64, B), dim3(64, 8), 0, st, part, v, flag, N,
-                       P, lm_in, lm_bin);
+                                const SkPair* pairs, hipStream_t st) {
+  if (pairs) {
+    if (P >= 64)
+      hipLaunchKernelGGL((sinkhorn_scaled_merge_ways_kernel<8, true>), dim3((N + 1 + 63) / 64, B), dim3(64, 8), 0, st, part, v,
+                         flag, N, P, lm_in, lm_bin, pairs);
+    else
+      hipLaunchKernelGGL(sinkhorn_scaled_merge_kernel<true>, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, flag,
+                         B, N, P, lm_in, lm_bin, pairs);
+  } else if (P >= 64) {
+    hipLaunchKernelGGL((sinkhorn_scaled_merge_ways_kernel<8, false>), dim3((N + 1 + 63) / 64, B), dim3(64, 8), 0, st, part, v,
+                       flag, N, P, lm_in, lm_bin, (const SkPair*)nullptr);
   } else {
-    hipLaunchKernelGGL(sinkhorn_scaled_merge_kernel, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, flag, B, N,
-                       P, lm_in, lm_bin);
+    hipLaunchKernelGGL(sinkhorn_scaled_merge_kernel<false>, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, flag,
+                       B, N, P, lm_in, lm_bin, (const SkPair*)nullptr);
   }
 }
 
 template <int K4>
 static void launch_fused(const float* scores, const float* v, float* u, float2* part, int B, int M, int N,
-                         const SkPlan& pl, float alpha, float lm_in, float mu_bin, hipStream_t st) {
+                         const SkPlan& pl, float alpha, float lm_in, float mu_bin, const SkPair* pairs, hipStream_t st) {
   // 16 chunks per lane: a row (64) + column statistics (128) exceed the 256 registers of two
   // waves per SIMD, so those run 4 waves per workgroup at one wave per SIMD
   constexpr int W = sk_waves(K4, true);
   const dim3 grid(B * pl.p), block(W * 64);
-  if (N % 4 == 0)
+  const SkPair* none = nullptr;
+  if (pairs) {
+    if (N % 4 == 0)
+      hipLaunchKernelGGL((sinkhorn_fused_kernel<K4, true, W, false, true>), grid, block, 0, st, scores, v, u, part, M, N,
+                         pl.rw, pl.p, alpha, lm_in, mu_bin, pairs);
+    else
+      hipLaunchKernelGGL((sinkhorn_fused_kernel<K4, false, W, false, true>), grid, block, 0, st, scores, v, u, part, M, N,
+                         pl.rw, pl.p, alpha, lm_in, mu_bin, pairs);
+  } else if (N % 4 == 0)
     hipLaunchKernelGGL((sinkhorn_fused_kernel<K4, true, W>), grid, block, 0, st, scores, v, u, part, M, N, pl.rw, pl.p,
-                       alpha, lm_in, mu_bin);
+                       alpha, lm_in, mu_bin, none);
   else
     hipLaunchKernelGGL((sinkhorn_fused_kernel<K4, false, W>), grid, block, 0, st, scores, v, u, part, M, N, pl.rw,
-                       pl.p, alpha, lm_in, mu_bin);
+                       pl.p, alpha, lm_in, mu_bin, none);
 }
 
 
 template <int K4>
 static void launch_scaled(const float* scores, const float* v, float* u, float* part, int B, int M, int N,
-                          const SkPlan& pl, float alpha, float lm_in, float mu_bin, bool nt, hipStream_t st) {
+                          const SkPlan& pl, float alpha, float lm_in, float mu_bin, bool nt, const SkPair* pairs,
+                          hipStream_t st) {
   constexpr int W = sk_waves(K4, false);
   const dim3 grid(B * pl.p), block(W * 64);
-  if (N % 4 == 0) {
+  const SkPair* none = nullptr;
+  if (pairs) {
+    if (N % 4 == 0) {
+      if (nt)
+        hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, true, W, true, true>), grid, block, 0, st, scores, v, u, part, M, N,
+                           pl.rw, pl.p, alpha, lm_in, mu_bin, pairs);
+      else
+        hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, true, W, false, true>), grid, block, 0, st, scores, v, u, part, M, N,
+                           pl.rw, pl.p, alpha, lm_in, mu_bin, pairs);
+    } else {
+      hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, false, W, false, true>), grid, block, 0, st, scores, v, u, part, M, N,
+                         pl.rw, pl.p, alpha, lm_in, mu_bin, pairs);
+    }
+  } else if (N % 4 == 0) {
     if (nt)
       hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, true, W, true>), grid, block, 0, st, scores, v, u, part, M, N, pl.rw,
-                         pl.p, alpha, lm_in, mu_bin);
+                         pl.p, alpha, lm_in, mu_bin, none);
     else
       hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, true, W, false>), grid, block, 0, st, scores, v, u, part, M, N,
-                         pl.rw, pl.p, alpha, lm_in, mu_bin);
+                         pl.rw, pl.p, alpha, lm_in, mu_bin, none);
   } else {
     hipLaunchKernelGGL((sinkhorn_scaled_kernel<K4, false, W, false>), grid, block, 0, st, scores, v, u, part, M, N, pl.rw,
-                       pl.p, alpha, lm_in, mu_bin);
+                       pl.p, alpha, lm_in, mu_bin, none);
   }
 }
 
@@ -703,7 +866,17 @@ static hipError_t sk_streams_for_device(SkStreams*& out) {
 // partial buffers (floats of (N+1)) one launch of pair group gb needs
 static size_t sk_group_parts(int gb, int M, int N) { return (size_t)gb * sk_plan(gb, M, N, false).p; }
 
-size_t sinkhorn_workspace_floats(int B, int M, int N) {
+static std::atomic<long long> g_sk_reruns{0};
+long long sinkhorn_exact_reruns() { return g_sk_reruns.load(); }
+static std::atomic<int> g_sk_force_exact{0};
+int sinkhorn_force_exact(int on) { return g_sk_force_exact.exchange(on ? 1 : 0); }
+
+// the per-pair table of a ragged batch sits behind everything else
+static size_t sk_pairs_floats(int B) { return (size_t)B * (sizeof(SkPair) / sizeof(float)) + 64; }
+static size_t sk_base_floats(int B, int M, int N);
+size_t sinkhorn_workspace_floats(int B, int M, int N) { return ((sk_base_floats(B, M, N) + 7) & ~size_t(7)) + sk_pairs_floats(B); }
+
+static size_t sk_base_floats(int B, int M, int N) {
   if (sk_fused_ok(M, N)) {  // [u | v | partials (max, sum) B x P x (N+1) | flag]
     const int G = sk_group(B, M, N);
     const int ns = G < B ? sk_streams_wanted((B + G - 1) / G) : 1;
@@ -715,19 +888,28 @@ size_t sinkhorn_workspace_floats(int B, int M, int N) {
 }
 
 hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M, int N, int iters, float* Z, float* ws,
-                                 hipStream_t st) {
+                                 hipStream_t st, const int* num0, const int* num1) {
   if (B == 0) return hipSuccess;
+  if ((num0 == nullptr) != (num1 == nullptr) || (num0 && (M <= 0 || N <= 0))) return hipErrorInvalidValue;
   // log_mu / log_nu (superglue.py:194-197), computed in fp32 like the reference
   const float ms = (float)M, ns = (float)N;
   const float norm = -logf(ms + ns);
   const float mu_bin = logf(ns) + norm, nu_bin = logf(ms) + norm;
   const bool fused = sk_fused_ok(M, N);
+  const SkPair* none = nullptr;
   float* sT = ws;
   float* u = fused ? ws : sT + (size_t)B * M * N;
   float* v = u + (size_t)B * (M + 1) + 64;
   hipError_t e;
   if ((e = hipMemsetAsync(u, 0, sizeof(float) * B * (M + 1), st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(v, 0, sizeof(float) * B * (N + 1), st)) != hipSuccess) return e;
+  // a ragged batch: the counts are clamped and the pairs' own marginals derived on the device
+  SkPair* pairs = nullptr;
+  if (num0) {
+    pairs = reinterpret_cast<SkPair*>(ws + ((sk_base_floats(B, M, N) + 7) & ~size_t(7)));
+    hipLaunchKernelGGL(sk_pairs_kernel, dim3((B + 255) / 256), dim3(256), 0, st, num0, num1, pairs, B, M, N, norm, mu_bin,
+                       nu_bin);
+  }
   if (fused) {
     float2* part = reinterpret_cast<float2*>(v + (size_t)B * (N + 1) + 64);
     const SkPlan pl = sk_plan(B, M, N, false), ple = sk_plan(B, M, N, true);
@@ -737,7 +919,8 @@ hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M,
     int* flag = reinterpret_cast<int*>(part + parts * (N + 1)) + 64;
     const int k4 = (N + 255) / 256;
     int low = 0;
-    if (kSkScaled) {
+    const bool scaled = kSkScaled && !g_sk_force_exact.load();  // test instrumentation: the exact kernels alone
+    if (scaled) {
       if ((e = hipMemsetAsync(flag, 0, sizeof(int), st)) != hipSuccess) return e;
       const int G = G0;
       // streaming schedule (one group of every pair): the scores pass the caches non-temporally;
@@ -762,13 +945,14 @@ hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M,
         const float* sc = scores + (size_t)b0 * M * N;
         float* ug = u + (size_t)b0 * (M + 1);
         float* vg = v + (size_t)b0 * (N + 1);
+        const SkPair* pgp = pairs ? pairs + b0 : nullptr;
         for (int it = 0; it < iters; ++it) {
-          if (k4 <= 1) launch_scaled<1>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, sq);
-          else if (k4 <= 2) launch_scaled<2>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, sq);
-          else if (k4 <= 4) launch_scaled<4>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, sq);
-          else if (k4 <= 8) launch_scaled<8>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, sq);
-          else launch_scaled<16>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, sq);
-          launch_scaled_merge(fp, vg, flag, gb, N, pg.p, norm, nu_bin, sq);
+          if (k4 <= 1) launch_scaled<1>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, pgp, sq);
+          else if (k4 <= 2) launch_scaled<2>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, pgp, sq);
+          else if (k4 <= 4) launch_scaled<4>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, pgp, sq);
+          else if (k4 <= 8) launch_scaled<8>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, pgp, sq);
+          else launch_scaled<16>(sc, vg, ug, fp, gb, M, N, pg, alpha, norm, mu_bin, nt, pgp, sq);
+          launch_scaled_merge(fp, vg, flag, gb, N, pg.p, norm, nu_bin, pgp, sq);
         }
       }
       if (ns > 1) {
@@ -783,31 +967,46 @@ hipError_t log_optimal_transport(const float* scores, float alpha, int B, int M,
       if ((e = hipMemcpyAsync(&low, flag, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
       if (low) {
+        g_sk_reruns.fetch_add(1);
         if ((e = hipMemsetAsync(u, 0, sizeof(float) * B * (M + 1), st)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(v, 0, sizeof(float) * B * (N + 1), st)) != hipSuccess) return e;
       }
     }
-    for (int it = 0; (!kSkScaled || low) && it < iters; ++it) {
-      if (k4 <= 1) launch_fused<1>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, st);
-      else if (k4 <= 2) launch_fused<2>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, st);
-      else if (k4 <= 4) launch_fused<4>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, st);
-      else if (k4 <= 8) launch_fused<8>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, st);
-      else launch_fused<16>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, st);
-      hipLaunchKernelGGL(sinkhorn_colmerge_kernel, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, B, N,
-                         ple.p, norm, nu_bin);
+    for (int it = 0; (!scaled || low) && it < iters; ++it) {
+      if (k4 <= 1) launch_fused<1>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, pairs, st);
+      else if (k4 <= 2) launch_fused<2>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, pairs, st);
+      else if (k4 <= 4) launch_fused<4>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, pairs, st);
+      else if (k4 <= 8) launch_fused<8>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, pairs, st);
+      else launch_fused<16>(scores, v, u, part, B, M, N, ple, alpha, norm, mu_bin, pairs, st);
+      if (pairs)
+        hipLaunchKernelGGL(sinkhorn_colmerge_kernel<true>, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, B, N,
+                           ple.p, norm, nu_bin, pairs);
+      else
+        hipLaunchKernelGGL(sinkhorn_colmerge_kernel<false>, dim3((B * (N + 1) + 255) / 256), dim3(256), 0, st, part, v, B, N,
+                           ple.p, norm, nu_bin, none);
     }
   } else {
-    if (M > 0 && N > 0)
-      hipLaunchKernelGGL(transpose_kernel, dim3((N + 63) / 64, (M + 63) / 64, B), dim3(256), 0, st, scores, sT, M, N);
+    const dim3 tg((N + 63) / 64, (M + 63) / 64, B);
+    if (pairs)
+      hipLaunchKernelGGL(transpose_kernel<true>, tg, dim3(256), 0, st, scores, sT, M, N, pairs);
+    else if (M > 0 && N > 0)
+      hipLaunchKernelGGL(transpose_kernel<false>, tg, dim3(256), 0, st, scores, sT, M, N, none);
   }
   for (int it = 0; !fused && it < iters; ++it) {
-    hipLaunchKernelGGL(lse_step_kernel, dim3((B * (M + 1) + 3) / 4), dim3(256), 0, st, scores, v, u, B, M, N, alpha, norm,
-                       mu_bin);
-    hipLaunchKernelGGL(lse_step_kernel, dim3((B * (N + 1) + 3) / 4), dim3(256), 0, st, sT, u, v, B, N, M, alpha, norm,
-                       nu_bin);
+    const dim3 gu((B * (M + 1) + 3) / 4), gv((B * (N + 1) + 3) / 4);
+    if (pairs) {
+      hipLaunchKernelGGL(lse_step_kernel<true>, gu, dim3(256), 0, st, scores, v, u, B, M, N, alpha, norm, mu_bin, pairs, 0);
+      hipLaunchKernelGGL(lse_step_kernel<true>, gv, dim3(256), 0, st, sT, u, v, B, N, M, alpha, norm, nu_bin, pairs, 1);
+    } else {
+      hipLaunchKernelGGL(lse_step_kernel<false>, gu, dim3(256), 0, st, scores, v, u, B, M, N, alpha, norm, mu_bin, none, 0);
+      hipLaunchKernelGGL(lse_step_kernel<false>, gv, dim3(256), 0, st, sT, u, v, B, N, M, alpha, norm, nu_bin, none, 0);
+    }
   }
-  hipLaunchKernelGGL(sinkhorn_out_kernel, dim3(B * (M + 1), (N + 1 + 1023) / 1024), dim3(256), 0, st, scores, u, v, Z, M,
-                     N, alpha, norm);
+  const dim3 og(B * (M + 1), (N + 1 + 1023) / 1024);
+  if (pairs)
+    hipLaunchKernelGGL(sinkhorn_out_kernel<true>, og, dim3(256), 0, st, scores, u, v, Z, M, N, alpha, norm, pairs);
+  else
+    hipLaunchKernelGGL(sinkhorn_out_kernel<false>, og, dim3(256), 0, st, scores, u, v, Z, M, N, alpha, norm, none);
   return hipGetLastError();
 }
 

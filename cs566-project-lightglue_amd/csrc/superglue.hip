@@ -23,6 +23,7 @@ constexpr int kEncMaxC = 256;
 __global__ __launch_bounds__(256) void sg_kenc_kernel(SgEncArgs a) {
   constexpr int AS = kEncMaxC + 4;  // LDS row stride (float4-aligned rows)
   __shared__ __attribute__((aligned(16))) float act[2][kEncRows][AS];
+  __shared__ int live[kEncRows];  // a ragged batch: the keypoint is a real point of its pair
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * kEncRows;
   const int nrow = min(kEncRows, a.rows - row0);
@@ -30,7 +31,9 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(SgEncArgs a) {
   if (tid < kEncRows) {
     const int r = row0 + tid;
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-    if (tid < nrow) {
+    const bool on = tid < nrow && (!a.cnt || r - (r / a.n) * a.n < a.cnt[r / a.n]);
+    live[tid] = on;
+    if (on) {
       const int b = r / a.n;
       const float w = a.size ? a.size[2 * b] : a.fw, h = a.size ? a.size[2 * b + 1] : a.fh;
       const float scale = fmaxf(w, h) * 0.7f;
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(SgEncArgs a) {
       }
       if (!last) {
         *reinterpret_cast<f32x4*>(&act[cur ^ 1][k][o]) = acc;
-      } else if (k < nrow) {
+      } else if (live[k]) {
         const size_t r = (size_t)(row0 + k);
         if (a.desc) {
           const f32x4 d = *reinterpret_cast<const f32x4*>(a.desc + r * kEncMaxC + o);

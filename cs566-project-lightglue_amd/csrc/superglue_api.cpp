@@ -99,6 +99,7 @@ struct Work {
   void *KP, *VP;
   _Float16 *Xp, *Cp, *Hp;
   unsigned* rtab;
+  int* cnt;  // a ragged batch: clamped counts [2B] (SegLayout order)
   int rows_pad;
   size_t bytes;
 };
@@ -127,6 +128,7 @@ Work carve(char* base, int B, int M, int N) {
   w.sws = (float*)take(lg::sinkhorn_workspace_floats(B, M, N) * 4);
   w.fws = (float*)take(lg::filter_workspace_floats(B, M, N) * 4);
   w.rtab = (unsigned*)take(kSlots * lg::kRangeStride * sizeof(unsigned));
+  w.cnt = (int*)take(2 * (size_t)B * sizeof(int));
   w.bytes = o;
   return w;
 }
@@ -422,8 +424,13 @@ int sg_workspace_bytes(const sg_handle_t* h, int32_t B, int32_t M, int32_t N, si
   return LG_OK;
 }
 
-int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* workspace, size_t workspace_bytes,
-               void* stream) {
+// n0 / n1 (both or neither): per-pair keypoint counts of a ragged batch, device int32 [B].  The
+// batch keeps its capacity layout (SegLayout: image 0 of pair b at rows b*M, image 1 at B*M + b*N);
+// the clamped counts mask the padding everywhere -- the encoder and the range statistics skip it,
+// every fp16x3 GEMM carries the live-row mask, the attention reads per-pair query / key counts,
+// and the cost GEMM sees zeroed md rows -- so pair b gets what it gets alone at its own sizes.
+static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0, const int32_t* n1, sg_outputs_t* out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
   using namespace lg;
   if (!h || !in || !out) return fail(LG_E_INVALID, "null argument");
   if (!h->loaded) return fail(LG_E_WEIGHTS, "weights not loaded");
@@ -456,6 +463,16 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
     g.bias = W + m.boff;
   };
   SG_HIP(hipMemsetAsync(rt, 0, kSlots * kRangeStride * sizeof(unsigned), st));
+  const bool ragged = n0 != nullptr;
+  const SegLayout SL{B, M, N};
+  RowMask live{};  // cnt == null without counts: every row live
+  const int *c0 = nullptr, *c1 = nullptr;
+  if (ragged) {
+    SG_HIP(ragged_counts(SL, n0, n1, w.cnt, st));
+    live = RowMask{w.cnt, nullptr, 1, SL};
+    c0 = w.cnt;
+    c1 = w.cnt + B;
+  }
 
   // ---- keypoint encoder + descriptors -> x (superglue.py:266-276).  enc_gemm: the hidden layers
   // in VALU into fp32 rows, their plane image, then the last layer as an fp16x3 GEMM whose residual
@@ -477,6 +494,7 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
     e.fh = (float)(s ? in->image_h1 : in->image_h0);
     e.n = s ? N : M;
     e.rows = B * e.n;
+    e.cnt = s ? c1 : c0;
     const size_t r0 = s ? (size_t)B * M : 0;
     if (h->enc_gemm) {
       e.desc = nullptr;
@@ -505,14 +523,21 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
   if (h->enc_gemm) {
     const int s_d = slot(), s_hr = slot(), s_he = slot();
     s_x = slot();
-    SG_HIP(range_absmax2(in->descriptors0, (size_t)B * M * D, in->descriptors1, (size_t)B * N * D, rt, s_d, st));
-    SG_HIP(range_absmax(w.ctx, (size_t)R * kl, rt, s_hr, st));
-    SG_HIP(rows_to_planes(w.ctx, R, kl, kl, w.Hp, RP, 0, ro(s_hr, 1.f, -1, 0.f, 0.f, s_he, 1), st));
+    if (ragged) {  // real rows only: the padding must not reach the range table
+      SG_HIP(range_absmax_rows(in->descriptors0, B * M, D, D, 0, live, rt, s_d, st));
+      SG_HIP(range_absmax_rows(in->descriptors1, B * N, D, D, B * M, live, rt, s_d, st));
+      SG_HIP(range_absmax_rows(w.ctx, R, kl, kl, 0, live, rt, s_hr, st));
+    } else {
+      SG_HIP(range_absmax2(in->descriptors0, (size_t)B * M * D, in->descriptors1, (size_t)B * N * D, rt, s_d, st));
+      SG_HIP(range_absmax(w.ctx, (size_t)R * kl, rt, s_hr, st));
+    }
+    SG_HIP(rows_to_planes(w.ctx, R, kl, kl, w.Hp, RP, 0, ro(s_hr, 1.f, -1, 0.f, 0.f, s_he, 1), st, nullptr,
+                          ragged ? &live : nullptr));
     GemmH3Args g;
     memset(&g, 0, sizeof(g));
     g.out_scale = 1.f;
     g.A0 = image(w.Hp, kl); g.K0 = kl; g.K = kl; wplanes(g, h->enc_last);
-    g.rtab = rt; g.a0_slot = s_he; g.a1_slot = -1;
+    g.rtab = rt; g.a0_slot = s_he; g.a1_slot = -1; g.rm = live;
     g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
     g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
     g.ro = ro(s_d, 1.f, s_he, h->enc_last.g, h->enc_last.bmax, s_x, 1);
@@ -520,8 +545,10 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
   } else {
     const int s_in = slot();
     s_x = slot();
-    SG_HIP(range_absmax(w.X, (size_t)R * D, rt, s_in, st));
-    SG_HIP(rows_to_planes(w.X, R, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st));
+    if (ragged) SG_HIP(range_absmax_rows(w.X, R, D, D, 0, live, rt, s_in, st));
+    else SG_HIP(range_absmax(w.X, (size_t)R * D, rt, s_in, st));
+    SG_HIP(rows_to_planes(w.X, R, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st, nullptr,
+                          ragged ? &live : nullptr));
   }
 
   // ---- AttentionalGNN (superglue.py:148-170)
@@ -542,7 +569,7 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
       g.rtab = rt; g.a0_slot = s_x; g.a1_slot = -1;
       g.ro = ro(s_x, ly.gK, -1, 0.f, ly.bK, s_k, 1);
       g.ro_v = ro(s_x, ly.gV, -1, 0.f, ly.bV, s_v, kRangeTrack | kRangeTwoSided);  // M[v] bounds the context (mlp.0's input)
-      g.R = R; g.Nout = 3 * D; g.hl = hl;
+      g.R = R; g.Nout = 3 * D; g.hl = hl; g.rm = live;
       SG_HIP(gemm_h3(g, EPI_QKV_ROT, st));
     }
     {
@@ -551,11 +578,11 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
       float* ctx1 = w.ctx + (size_t)B * M * D;
       AttnSet a0, a1;
       if (ly.type == 0) {  // self: layer(desc0, desc0), layer(desc1, desc1)
-        a0 = {w.Q, w.KP, w.VP, ps, w.ctx, M, M, w.Cp, (long long)RP * D, RP, 0, rt, s_k, nullptr, nullptr, nullptr};
-        a1 = {w.Q + img1, kp1, vp1, ps, ctx1, N, N, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, nullptr, nullptr, nullptr};
+        a0 = {w.Q, w.KP, w.VP, ps, w.ctx, M, M, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c0, nullptr};
+        a1 = {w.Q + img1, kp1, vp1, ps, ctx1, N, N, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c1, nullptr};
       } else {  // cross: layer(desc0, desc1), layer(desc1, desc0)
-        a0 = {w.Q, kp1, vp1, ps, w.ctx, M, N, w.Cp, (long long)RP * D, RP, 0, rt, s_k, nullptr, nullptr, nullptr};
-        a1 = {w.Q + img1, w.KP, w.VP, ps, ctx1, N, M, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, nullptr, nullptr, nullptr};
+        a0 = {w.Q, kp1, vp1, ps, w.ctx, M, N, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c1, nullptr};
+        a1 = {w.Q + img1, w.KP, w.VP, ps, ctx1, N, M, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c0, nullptr};
       }
       SG_HIP(attention_f32(a0, a1, B, H, 0.125f, PREC_H3, st));  // 1 / sqrt(dim = 64) (:108)
     }
@@ -568,7 +595,7 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
       g.out_scale = 1.f;
       g.A0 = image(w.Xp, D); g.K0 = D; g.A1 = image(w.Cp, D); g.K = 2 * D; wplanes(g, ly.w1);
       g.rtab = rt; g.a0_slot = s_x; g.a1_slot = s_v;
-      g.R = R; g.Nout = 2 * D; g.relu = 1;
+      g.R = R; g.Nout = 2 * D; g.relu = 1; g.rm = live;
       g.Yp = w.Hp; g.yps = (long long)RP * 2 * D; g.yrows_pad = RP;
       g.ro = ro(s_x, ly.w1.g, s_v, ly.w1.g, ly.w1.bmax, s_h, 1);
       SG_HIP(gemm_h3(g, EPI_STORE, st));
@@ -578,7 +605,7 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
       memset(&g, 0, sizeof(g));
       g.out_scale = 1.f;
       g.A0 = image(w.Hp, 2 * D); g.K0 = 2 * D; g.K = 2 * D; wplanes(g, ly.w2);
-      g.rtab = rt; g.a0_slot = s_h; g.a1_slot = -1;
+      g.rtab = rt; g.a0_slot = s_h; g.a1_slot = -1; g.rm = live;
       g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
       g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
       g.ro = ro(s_x, 1.f, s_h, ly.w2.g, ly.w2.bmax, s_xn, 1);
@@ -586,6 +613,7 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
     }
     s_x = s_xn;
   }
+  if (ragged) SG_HIP(zero_dead_rows(w.X, R, D, 0, live, st));  // padded rows leave as zeros, not stale workspace
   if (out->descriptors0)
     SG_HIP(hipMemcpyAsync(out->descriptors0, w.X, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
   if (out->descriptors1)
@@ -598,9 +626,11 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
     g.out_scale = 1.f;
     g.A0 = image(w.Xp, D); g.K0 = D; g.K = D; wplanes(g, h->fin);
     g.rtab = rt; g.a0_slot = s_x; g.a1_slot = -1;
-    g.R = R; g.Nout = D; g.Y = w.md; g.ldy = D;
+    g.R = R; g.Nout = D; g.Y = w.md; g.ldy = D; g.rm = live;
     SG_HIP(gemm_h3(g, EPI_STORE, st));
   }
+  // zero md rows of the padding: the cost is then 0 (and finite) outside the pair's real block
+  if (ragged) SG_HIP(zero_dead_rows(w.md, R, D, 0, live, st));
   float* cost = out->sinkhorn_cost ? out->sinkhorn_cost : w.cost;
   {
     GemmArgs g;
@@ -612,10 +642,22 @@ int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* w
     SG_HIP(gemm_x6(g, EPI_STORE, B, st));
   }
   float* Z = out->log_assignment ? out->log_assignment : w.Z;
-  SG_HIP(log_optimal_transport(cost, h->bin_score, B, M, N, h->cfg.sinkhorn_iterations, Z, w.sws, st));
+  SG_HIP(log_optimal_transport(cost, h->bin_score, B, M, N, h->cfg.sinkhorn_iterations, Z, w.sws, st, c0, c1));
   SG_HIP(filter_from_scores(Z, B, M, N, h->cfg.filter_threshold, w.fws, out->matches0, out->matches1,
-                            out->matching_scores0, out->matching_scores1, st));
+                            out->matching_scores0, out->matching_scores1, st, ragged ? w.cnt : nullptr));
   return LG_OK;
+}
+
+int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* workspace, size_t workspace_bytes,
+               void* stream) {
+  return forward_impl(h, in, nullptr, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int sg_forward_ragged(sg_handle_t* h, const sg_inputs_t* in, const int32_t* num_keypoints0, const int32_t* num_keypoints1,
+                      sg_outputs_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if ((num_keypoints0 == nullptr) != (num_keypoints1 == nullptr))
+    return fail(LG_E_INVALID, "num_keypoints0 and num_keypoints1 must be given together");
+  return forward_impl(h, in, num_keypoints0, num_keypoints1, out, workspace, workspace_bytes, stream);
 }
 
 static int nll_loss(const float* la, int32_t B, int32_t M, int32_t N, const uint8_t* gta, const int64_t* gt0,

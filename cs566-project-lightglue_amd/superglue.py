@@ -19,7 +19,14 @@ Deliberate differences from the reference:
   ``torch.utils.checkpoint`` recomputation makes (:151-155); ``loss`` is differentiable through
   ``sg_nll_backward``;
 * ``NLLLoss`` with explicit ``weights`` other than the ground truth's raises NotImplementedError
-  (the kernel derives the weights from the ground truth, losses.py:46-73).
+  (the kernel derives the weights from the ground truth, losses.py:46-73);
+* ragged batches: ``data["num_keypoints0/1"]`` (integer ``[B]``, given together; what ``SuperPoint``
+  and ``SuperPointOpen`` emit) make pair ``b`` match as it would alone at ``M = n0[b]``, ``N = n1[b]``
+  (``sg_forward_ragged``).  Padding may hold anything, NaN included; padded points get ``-1`` / ``0``,
+  ``sinkhorn_cost`` is 0 outside the pair's block, ``log_assignment`` keeps its ``[B, M+1, N+1]``
+  shape with the dustbins at ``M`` / ``N`` and ``-inf`` elsewhere, a pair with an empty image has no
+  matches.  The ``[-1, 1]`` assert reads real points only.  Training mode with counts raises
+  NotImplementedError (BatchNorm batch statistics over a ragged batch are out of scope).
 """
 import ctypes
 
@@ -27,7 +34,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .lightglue import merge_conf
+from .lightglue import LightGlue, merge_conf
 from .sg_weights import SG_DEFAULT_CONF
 
 
@@ -181,6 +188,10 @@ class SuperGlue(nn.Module):
             assert k in data, f"Missing key {k} in data"
         c = self.conf
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
+        nk0, nk1 = LightGlue._check_counts(data.get("num_keypoints0"), data.get("num_keypoints1"), kpts0.shape[0])
+        if nk0 is not None and self.training:
+            raise NotImplementedError("lightglue_amd.SuperGlue: num_keypoints0/1 (ragged batches) are not supported in "
+                                      "training mode (BatchNorm batch statistics); pad or batch equal counts")
         if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:  # no keypoints (:257-264)
             shape0, shape1 = kpts0.shape[:-1], kpts1.shape[:-1]
             return {
@@ -203,11 +214,18 @@ class SuperGlue(nn.Module):
 
         s0, w0, h0 = size_of(data["view0"])
         s1, w1, h1 = size_of(data["view1"])
-        # the reference asserts every normalised keypoint lies in [-1, 1] (:272-273)
-        for k, s, w, h in ((kpts0, s0, w0, h0), (kpts1, s1, w1, h1)):
+        if nk0 is not None:  # device int32 [B]; clamped on the device, never read on the host
+            nk0 = nk0.to(device=device, dtype=torch.int32).contiguous()
+            nk1 = nk1.to(device=device, dtype=torch.int32).contiguous()
+        # the reference asserts every normalised keypoint lies in [-1, 1] (:272-273); of a ragged
+        # batch, every real one (the padding may hold anything)
+        for k, s, w, h, nk in ((kpts0, s0, w0, h0, nk0), (kpts1, s1, w1, h1, nk1)):
             size = s if s is not None else torch.tensor([[float(w), float(h)]], device=device)
             kn = (k.float() - (size / 2)[:, None]) / (size.max(1).values * 0.7)[:, None, None]
-            assert torch.all(kn >= -1) and torch.all(kn <= 1)
+            ok = (kn >= -1) & (kn <= 1)
+            if nk is not None:
+                ok = ok | (torch.arange(k.shape[1], device=device)[None, :] >= nk[:, None])[..., None]
+            assert torch.all(ok)
 
         def f32(t):
             return t.to(device=device, dtype=torch.float32).contiguous()
@@ -234,7 +252,12 @@ class SuperGlue(nn.Module):
         g1 = torch.empty((B, N, 256), device=device) if return_descriptors else None
         out = _lib.SGOutputs(_ptr(m0), _ptr(m1), _ptr(ms0), _ptr(ms1), _ptr(cost), _ptr(la), _ptr(g0), _ptr(g1))
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(lib.sg_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(ws), nb, stream), "sg_forward")
+        if nk0 is not None:
+            _lib.check(lib.sg_forward_ragged(self._handle, ctypes.byref(inp), _ptr(nk0), _ptr(nk1), ctypes.byref(out),
+                                             _ptr(ws), nb, stream), "sg_forward_ragged")
+        else:
+            _lib.check(lib.sg_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(ws), nb, stream),
+                       "sg_forward")
         pred = {"sinkhorn_cost": cost, "log_assignment": la, "matches0": m0, "matches1": m1, "matching_scores0": ms0,
                 "matching_scores1": ms1}
         if return_descriptors:

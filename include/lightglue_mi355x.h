@@ -221,6 +221,14 @@ int lg_filter_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes);
 int lg_filter_matches(const float* scores, int32_t B, int32_t M, int32_t N, double threshold,
                       int64_t* matches0, int64_t* matches1, float* scores0, float* scores1,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* The same on a ragged batch: num0 / num1 are device int32 [B] (clamped on the device to [0, M] /
+ * [0, N], never read on the host).  The argmaxes run over pair b's real block (i < num0[b],
+ * j < num1[b]) of the fixed-shape scores; padded points get -1 / 0, and so does every point of a
+ * pair with an empty image.  Both NULL: lg_filter_matches; one NULL: LG_E_INVALID.  Same workspace. */
+int lg_filter_matches_ragged(const float* scores, int32_t B, int32_t M, int32_t N, double threshold,
+                             const int32_t* num0, const int32_t* num1, int64_t* matches0, int64_t* matches1,
+                             float* scores0, float* scores1, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* log_optimal_transport (superglue.py:181-201): Z [B,M+1,N+1] = log-domain Sinkhorn of
  * `scores` [B,M,N] with a dustbin of score `alpha`, `iters` iterations, multiplied by M+N.
@@ -231,6 +239,22 @@ int lg_sinkhorn_workspace_bytes(int32_t B, int32_t M, int32_t N, size_t* bytes);
 int lg_log_optimal_transport(const float* scores, float alpha, int32_t B, int32_t M, int32_t N,
                              int32_t iters, float* Z, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* The same on a ragged batch (M, N >= 1 are the capacities): pair b has num0[b] <= M rows and
+ * num1[b] <= N columns, stored first; the rest of its [M][N] slot is arbitrary (NaN allowed).  The
+ * counts are device int32 [B], clamped on the device and never read on the host.  Pair b gets what
+ * it gets alone at its own sizes (marginals from -log(num0 + num1)), inside the fixed-shape Z: real
+ * block at i < num0, j < num1, dustbin column at N (i < num0), dustbin row at M (j < num1), corner
+ * [M][N], every other entry -inf.  A pair with num0 == 0 or num1 == 0 is -inf except [M][N] = 0.
+ * Padded columns neither raise the underflow flag nor enter a merge; the exact rerun is ragged too.
+ * Both NULL: lg_log_optimal_transport; one NULL: LG_E_INVALID.  Same workspace. */
+int lg_log_optimal_transport_ragged(const float* scores, float alpha, int32_t B, int32_t M, int32_t N,
+                                    const int32_t* num0, const int32_t* num1, int32_t iters, float* Z,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+/* how often this process reran the exact kernel after the scaled one flagged an underflow */
+int64_t lg_sinkhorn_rerun_count(void);
+/* test instrumentation (process-wide): on != 0 makes N <= 4096 run the exact running-max kernels
+ * alone, without the scaled pass and its flag read-back; returns the previous setting */
+int lg_sinkhorn_force_exact(int on);
 
 /* Homography ground truth: gt_matches_from_homography (gluefactory/geometry/gt_generation.py:109-161
  * with warp_points_torch, geometry/homography.py:161-180), what matchers.homography_matcher computes

@@ -77,6 +77,16 @@ int sg_workspace_bytes(const sg_handle_t* h, int32_t B, int32_t M, int32_t N, si
 /* eval forward; M, N >= 1 (the caller handles the empty case, superglue.py:257-264) */
 int sg_forward(sg_handle_t* h, const sg_inputs_t* in, sg_outputs_t* out, void* workspace, size_t workspace_bytes,
                void* stream);
+/* The eval forward on a ragged batch: pair b has num_keypoints0[b] <= M and num_keypoints1[b] <= N
+ * real points, stored first; the rest of each slot is arbitrary (NaN allowed) in keypoints,
+ * descriptors and scores.  Counts are device int32 [B], clamped on the device to [0, capacity] and
+ * never read on the host.  Pair b gets what it gets alone at its own sizes, in the capacity layout:
+ * matches -1 / scores 0 on padded points, sinkhorn_cost 0 and descriptors 0 outside the real block,
+ * log_assignment as lg_log_optimal_transport_ragged lays it out.  A pair with an empty image has no
+ * matches and runs nothing.  Both NULL: sg_forward; one NULL: LG_E_INVALID.  Same workspace. */
+int sg_forward_ragged(sg_handle_t* h, const sg_inputs_t* in, const int32_t* num_keypoints0,
+                      const int32_t* num_keypoints1, sg_outputs_t* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
 /* NLL of a log assignment [B][M+1][N+1]; gt_assignment [B][M][N] (0/1 bytes), gt_matches [B][M] /
  * [B][N] (-1 = unmatched).  out [5][B]: nll, nll_pos, nll_neg, num_matchable, num_unmatchable.
  * mode 0: SuperGlue.loss; mode 1: NLLLoss (requires M == N, as the reference's indexing does) */
