@@ -42,6 +42,12 @@ EXPORTED_SYMBOLS = [
     "lg_linear_workspace_bytes",
     "lg_linear",
     "lg_plane_roundtrip",
+    # kernel-level SuperPoint convolution and dense-head entries (ABI 12, no handle)
+    "sp_conv_layer_workspace_bytes",
+    "sp_conv_layer_rows",
+    "sp_conv_layer",
+    "sp_head_scores",
+    "sp_head_normalize",
     # kernel-level assignment entry (ABI 12, no handle)
     "lg_assign_workspace_bytes",
     "lg_assign",
@@ -265,6 +271,28 @@ class LGLinearArgs(ctypes.Structure):  # lg_linear_args_t
     ]
 
 
+class SPConvLayerArgs(ctypes.Structure):  # sp_conv_layer_args_t
+    _fields_ = [
+        ("B", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("Cin", ctypes.c_int32),
+        ("Cout", ctypes.c_int32),
+        ("pool", ctypes.c_int32),
+        ("conv1a", ctypes.c_int32),
+        ("x", _P),
+        ("w", _P),
+        ("bias", _P),
+        ("post_scale", _P),
+        ("post_shift", _P),
+        ("y_rows", _P),
+        ("y_planes", _P),
+        ("exp_in", ctypes.POINTER(ctypes.c_int32)),
+        ("exp_out", ctypes.POINTER(ctypes.c_int32)),
+        ("max_out", ctypes.POINTER(ctypes.c_float)),
+    ]
+
+
 class SPConfig(ctypes.Structure):  # sp_config_t
     _fields_ = [
         ("has_detector", ctypes.c_int32),
@@ -446,6 +474,11 @@ def load():
         "lg_linear_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_linear": (ctypes.c_int, [ctypes.POINTER(LGLinearArgs), _P, sz, _P]),
         "lg_plane_roundtrip": (ctypes.c_int, [_P, i32, i32, i32, i32, _P, ctypes.POINTER(i32), _P]),
+        "sp_conv_layer_workspace_bytes": (ctypes.c_int, [i32] * 7 + [ctypes.POINTER(sz)]),
+        "sp_conv_layer_rows": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]),
+        "sp_conv_layer": (ctypes.c_int, [ctypes.POINTER(SPConvLayerArgs), _P, sz, _P]),
+        "sp_head_scores": (ctypes.c_int, [_P, i32, i32, i32, i32, _P, _P]),
+        "sp_head_normalize": (ctypes.c_int, [_P, i32, _P, _P]),
         "lg_assign_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_assign": (ctypes.c_int, [ctypes.POINTER(LGAssignArgs), _P, sz, _P]),
         "lg_assignment_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(sz)]),

@@ -543,6 +543,57 @@ int lg_plane_roundtrip(const float* x, int32_t R, int32_t K, int32_t lshift, int
                        int32_t* exponent, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Kernel-level checks of the SuperPoint convolutions (tests; the reference's counterpart is one
+ * nn.Conv2d(3x3, padding 1) + ReLU, the open model's BatchNorm as an affine, and max_pool2d(2)):
+ * one launch of sp_conv3x3 -- or, with conv1a, of sp_conv1a -- on plain fp32 device tensors,
+ * prepared inside the workspace the way sp_load_weights and sp_forward prepare them.  No handle.
+ * Additive: the ABI version does not move.
+ *   x           [B][H][W][Cin] (NHWC rows); conv1a: the image [B][Cin][H][W], Cin = 1 or 3 (RGB is
+ *               reduced to gray first), and Cout == 64
+ *   w           [Cout][Cin][3][3] (conv1a: [64][1][3][3]), bias [Cout]
+ *   post_scale, post_shift  [Cout], both or neither: y = relu(conv + bias) * s + t before the pool
+ *   pool        2x2 max-pool (floor) fused behind it (not for conv1a)
+ * Preparation: a zeroed range table; max|x| into a slot; x as a plane image with a two-sided range
+ * exponent chosen from it (rows past B*H*W zeroed: the taps outside the image read one of them); the
+ * weight repacked to [Cout][9 Cin], split into planes of W * 2^sw (max|W 2^sw| in [8, 16)); the
+ * output range bound g M[x] + max|bias| from the weight's largest row L1 norm g, with the affine
+ * max|s| (g M[x] + max|bias|) + max|t|.  The route (halo tiles, or the per-tap gather under
+ * LG_SP_CONV=gather) is the one sp_conv3x3 reads from the environment at launch.
+ * Outputs: y_planes, the raw output image: 2 planes [Cout / 32][yrows_pad][32] fp16 (h, l * 2^11;
+ * times 2^exp_out), rout live rows, both from sp_conv_layer_rows; y_rows [rout][Cout] (nullable), the
+ * image decoded; on the host (nullable) the exponents the input and output images were written with
+ * and the recorded max|y|.  Rows [rout, yrows_pad) of y_planes are never written.
+ * LG_E_INVALID (nothing launched, nothing written): a null required pointer, a non-positive size,
+ * Cin % 32, Cout % 64, pool with H < 2 or W < 2, post_scale without post_shift (or the reverse), a
+ * pointer off 16 bytes; conv1a: Cin not 1 or 3, Cout != 64, pool.  LG_E_WORKSPACE: workspace smaller
+ * than sp_conv_layer_workspace_bytes.  Synchronises the stream before returning. */
+typedef struct {
+  int32_t B, H, W, Cin, Cout;
+  int32_t pool, conv1a;
+  const float* x;
+  const float* w;
+  const float* bias;
+  const float* post_scale;      /* [Cout] or NULL */
+  const float* post_shift;
+  float* y_rows;                /* [rout][Cout] or NULL */
+  void* y_planes;               /* 2 * yrows_pad * Cout fp16 */
+  int32_t* exp_in;              /* host out (nullable); conv1a: 0 */
+  int32_t* exp_out;
+  float* max_out;
+} sp_conv_layer_args_t;
+int sp_conv_layer_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool,
+                                  int32_t conv1a, size_t* bytes);
+/* rows of the output image: *rout live ones, *yrows_pad allocated (a multiple of 256, > *rout) */
+int sp_conv_layer_rows(int32_t B, int32_t H, int32_t W, int32_t pool, int64_t* rout, int32_t* yrows_pad);
+int sp_conv_layer(const sp_conv_layer_args_t* args, void* workspace, size_t workspace_bytes, void* stream);
+/* The two dense-head kernels alone (stream-ordered, asynchronous).
+ * sp_head_scores: logits [B * Hc * Wc][ld] (ld >= 65, 65 used) -> softmax over the 65 without the
+ * dustbin, unfolded: scores [B][8 Hc][8 Wc], scores[b][8y + dy][8x + dx] = p[cell (y, x)][8 dy + dx].
+ * sp_head_normalize: rows of 256 -> x / max(|x|_2, 1e-12) (in place allowed). */
+int sp_head_scores(const float* logits, int32_t ld, int32_t B, int32_t Hc, int32_t Wc, float* scores, void* stream);
+int sp_head_normalize(const float* x, int32_t rows, float* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Kernel-level checks of the assignment head (lightglue.py:284-296, 306-315, 321-337): the dual
  * softmax and the mutual filter alone, on the caller's matching descriptors md0 [B][M][256] /
  * md1 [B][N][256], matchability logits z0 [B][M] / z1 [B][N] and (nullable, device) per-pair counts.
