@@ -24,6 +24,10 @@ def __getattr__(name):
         from .superpoint_open import SuperPoint
 
         return SuperPoint
+    if name == "ALIKED":
+        from .aliked import ALIKED
+
+        return ALIKED
     if name in ("SuperGlue", "NLLLoss"):
         from . import superglue
 

@@ -98,6 +98,18 @@ EXPORTED_SYMBOLS = [
     "sp_workspace_bytes",
     "sp_forward",
     "sp_sample_descriptors",
+    # ALIKED extractor (include/aliked_mi355x.h; ABI 12, additive)
+    "sp_aliked_create",
+    "sp_aliked_destroy",
+    "sp_aliked_weight_count",
+    "sp_aliked_weight_name",
+    "sp_aliked_weight_numel",
+    "sp_aliked_load_weights",
+    "sp_aliked_workspace_bytes",
+    "sp_aliked_forward",
+    "sp_aliked_deform_conv",
+    "sp_aliked_set_profile",
+    "sp_aliked_stage_ms",
     "sg_create",
     "sg_destroy",
     "sg_weight_count",
@@ -341,6 +353,43 @@ class SPOutputs(ctypes.Structure):  # sp_outputs_t
     ]
 
 
+class AlikedConfig(ctypes.Structure):  # sp_aliked_config_t
+    _fields_ = [
+        ("c1", ctypes.c_int32),
+        ("c2", ctypes.c_int32),
+        ("c3", ctypes.c_int32),
+        ("c4", ctypes.c_int32),
+        ("dim", ctypes.c_int32),
+        ("M", ctypes.c_int32),
+        ("nms_radius", ctypes.c_int32),
+        ("max_num_keypoints", ctypes.c_int32),
+        ("detection_threshold", ctypes.c_float),
+    ]
+
+
+class AlikedInputs(ctypes.Structure):  # sp_aliked_inputs_t
+    _fields_ = [
+        ("B", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("image", _P),
+        ("image_size", _P),
+    ]
+
+
+class AlikedOutputs(ctypes.Structure):  # sp_aliked_outputs_t
+    _fields_ = [
+        ("score_map", _P),
+        ("capacity", ctypes.c_int32),
+        ("keypoints", _P),
+        ("descriptors", _P),
+        ("sampled_scores", _P),
+        ("dispersity", _P),
+        ("counts", _P),
+        ("host_counts", _P),
+    ]
+
+
 SG_MAX_LAYERS = 64
 SG_MAX_KENC = 7
 
@@ -563,6 +612,20 @@ def load():
         "sp_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "sp_forward": (ctypes.c_int, [_P, ctypes.POINTER(SPInputs), ctypes.POINTER(SPOutputs), _P, sz, _P]),
         "sp_sample_descriptors": (ctypes.c_int, [_P, _P, _P, i32, i32, _P, _P, sz, _P]),
+        "sp_aliked_create": (ctypes.c_int, [ctypes.POINTER(AlikedConfig), ctypes.c_int, ctypes.POINTER(_P)]),
+        "sp_aliked_destroy": (ctypes.c_int, [_P]),
+        "sp_aliked_weight_count": (ctypes.c_int, [_P]),
+        "sp_aliked_weight_name": (ctypes.c_char_p, [_P, ctypes.c_int]),
+        "sp_aliked_weight_numel": (ctypes.c_int64, [_P, ctypes.c_int]),
+        "sp_aliked_load_weights": (
+            ctypes.c_int,
+            [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), _P],
+        ),
+        "sp_aliked_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "sp_aliked_forward": (ctypes.c_int, [_P, ctypes.POINTER(AlikedInputs), ctypes.POINTER(AlikedOutputs), _P, sz, _P]),
+        "sp_aliked_deform_conv": (ctypes.c_int, [_P, _P, _P, _P, i32, i32, i32, i32, i32, _P, _P, sz, _P]),
+        "sp_aliked_set_profile": (ctypes.c_int, [_P, i32]),
+        "sp_aliked_stage_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
         "sg_create": (ctypes.c_int, [ctypes.POINTER(SGConfig), ctypes.c_int, ctypes.POINTER(_P)]),
         "sg_destroy": (ctypes.c_int, [_P]),
         "sg_weight_count": (ctypes.c_int, [_P]),

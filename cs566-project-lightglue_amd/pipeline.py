@@ -9,7 +9,8 @@ model registry that resolve the matcher by name.
   HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.depth_matcher"`` to the
   pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
   the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
-  the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`).  Other components (filters,
+  the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`); ``"extractors.aliked"`` to ALIKED
+  (:mod:`~lightglue_amd.aliked`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -195,7 +196,13 @@ def _nn_matcher():
     return NearestNeighborMatcher
 
 
-_LAZY = (_superpoint, _superpoint_open, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
+def _aliked():
+    from .aliked import ALIKED
+
+    return ALIKED
+
+
+_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -210,6 +217,9 @@ _REGISTRY = {
     # the open (MIT) SuperPoint (models/extractors/superpoint_open.py), resolved lazily
     "extractors.superpoint_open": _superpoint_open,
     "superpoint_open": _superpoint_open,
+    # ALIKED (models/extractors/aliked.py), resolved lazily
+    "extractors.aliked": _aliked,
+    "aliked": _aliked,
     # the SuperGlue matcher (gluefactory_nonfree/superglue.py), resolved lazily
     "gluefactory_nonfree.superglue": _superglue,
     "superglue": _superglue,
