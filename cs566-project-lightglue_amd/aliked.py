@@ -44,9 +44,9 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._native import NativeModule, _ptr
 from .aliked_weights import ALIKED_CFGS, ALIKED_DEFAULT_CONF
 from .lightglue import merge_conf
-from .superpoint import _ptr
 
 
 class DeformableConv2d(nn.Module):  # aliked.py:270-305 (mask=False)
@@ -90,7 +90,9 @@ class SDDH(nn.Module):  # aliked.py:458-511 (conv2D=False, mask=False)
         self.register_parameter("agg_weights", nn.Parameter(torch.rand(n_pos, dims, dims)))
 
 
-class ALIKED(nn.Module):
+class ALIKED(NativeModule):
+    _native_prefix = "sp_aliked"
+    _native_name = "lightglue_amd.ALIKED: parameter"
     default_conf = ALIKED_DEFAULT_CONF
     required_data_keys = ["image"]
     checkpoint_url = "https://github.com/Shiaoming/ALIKED/raw/main/models/{}.pth"
@@ -129,10 +131,7 @@ class ALIKED(nn.Module):
             for p in self.parameters():
                 p.requires_grad = False
         self._owners = [m for m in self.modules() if m._parameters or isinstance(m, nn.BatchNorm2d)]
-        self._handle = None
-        self._handle_device = None
-        self._weights_key = None
-        self._ws = None
+        self._native_init()
 
     # ------------------------------------------------------------ native handle
     def _native_state(self):
@@ -147,52 +146,11 @@ class ALIKED(nn.Module):
                 sig += [(id(m), n, m._buffers[n].data_ptr(), m._buffers[n]._version) for n in ("running_mean", "running_var")]
         return tuple(sig)
 
-    def _ensure_handle(self, device):
-        lib = _lib.load()
-        if self._handle is not None and self._handle_device != device:
-            lib.sp_aliked_destroy(self._handle)
-            self._handle = None
-        if self._handle is None:
-            c, g = self.conf, self.cfgs[self.conf.model_name]
-            cfg = _lib.AlikedConfig(g["c1"], g["c2"], g["c3"], g["c4"], g["dim"], g["M"], int(c.nms_radius),
-                                    int(c.max_num_keypoints), float(c.detection_threshold))
-            h = ctypes.c_void_p()
-            _lib.check(lib.sp_aliked_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sp_aliked_create")
-            self._handle, self._handle_device, self._weights_key = h, device, None
-        key = self._weights_signature()
-        if key != self._weights_key:
-            sd = self._native_state()
-            names = list(sd)
-            ts = []
-            for n in names:
-                t = sd[n].detach()
-                if t.device != device or t.dtype != torch.float32:
-                    raise RuntimeError(f"lightglue_amd.ALIKED: parameter {n} is {t.dtype} on {t.device}; "
-                                       f"move the module to {device} in fp32")
-                ts.append(t.contiguous())
-            arr_n = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
-            arr_p = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-            arr_k = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.sp_aliked_load_weights(self._handle, len(ts), arr_n, arr_p, arr_k, ctypes.c_void_p(stream)),
-                       "sp_aliked_load_weights")
-            torch.cuda.current_stream(device).synchronize()
-            self._weights_key = key
-        return lib
-
-    def reload_weights(self):
-        self._weights_key = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self._weights_key = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.sp_aliked_destroy(self._handle)
-        except Exception:
-            pass
+    def _create_handle(self, lib, device, h):
+        c, g = self.conf, self.cfgs[self.conf.model_name]
+        cfg = _lib.AlikedConfig(g["c1"], g["c2"], g["c3"], g["c4"], g["dim"], g["M"], int(c.nms_radius),
+                                int(c.max_num_keypoints), float(c.detection_threshold))
+        _lib.check(lib.sp_aliked_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sp_aliked_create")
 
     # ------------------------------------------------------------ forward (aliked.py:765-783)
     def forward(self, data: dict) -> dict:
@@ -212,8 +170,7 @@ class ALIKED(nn.Module):
         lib = self._ensure_handle(device)
         nb = ctypes.c_size_t()
         _lib.check(lib.sp_aliked_workspace_bytes(self._handle, B, H, W, cap, ctypes.byref(nb)), "sp_aliked_workspace_bytes")
-        if self._ws is None or self._ws.numel() < nb.value or self._ws.device != device:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=device)
+        ws = self._workspace_bytes(nb.value, device)
         isz = data.get("image_size")
         isz = None if isz is None else isz.to(device=device, dtype=torch.float32).contiguous()
         score_map = torch.empty((B, 1, H, W), device=device)
@@ -227,7 +184,7 @@ class ALIKED(nn.Module):
         out = _lib.AlikedOutputs(_ptr(score_map), cap, _ptr(kpts), _ptr(desc), _ptr(sampled), _ptr(disp), _ptr(counts),
                                  ctypes.cast(host_counts, ctypes.c_void_p))
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(lib.sp_aliked_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(self._ws), nb.value, stream),
+        _lib.check(lib.sp_aliked_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(ws), nb.value, stream),
                    "sp_aliked_forward")
         n = list(host_counts)
         pred = {"score_map": score_map}

@@ -5,36 +5,19 @@
 
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/aliked_mi355x.h"
 #include "../../include/lightglue_mi355x.h"
 #include "aliked.h"
+#include "api_common.h"
 #include "kernels.h"
-
-namespace lg {
-int api_fail(int code, const char* msg);
-}
 
 namespace {
 
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define AK_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr float kBnEps = 1e-5f;      // nn.BatchNorm2d default
 constexpr int kNLimitMax = 20000;    // aliked.py:603
-
-struct Tensor {
-  std::string name;
-  int64_t numel;
-};
 
 // how a convolution's weights reach the kernels
 enum Kind { K_BN3, K_BIAS3, K_BIAS1, K_PLAIN1, K_PLAIN3, K_SLICE1 };
@@ -60,7 +43,7 @@ size_t a64(size_t n) { return (n + 63) & ~size_t(63); }  // floats: 256-byte ste
 struct sp_aliked_handle {
   sp_aliked_config_t cfg;
   int device;
-  std::vector<Tensor> schema;
+  lg::WeightSchema schema;
   std::vector<Layer> layers;
   float* gbuf = nullptr;
   size_t gfloats = 0;
@@ -105,45 +88,45 @@ void build(sp_aliked_handle* h) {
   // the reference's state_dict order (a module's own parameters before its children's)
   auto& S = h->schema;
   auto bn = [&](const std::string& n, int ch) {
-    for (const char* t : {"weight", "bias", "running_mean", "running_var"}) S.push_back({n + "." + t, ch});
+    for (const char* t : {"weight", "bias", "running_mean", "running_var"}) S.add(n + "." + t, ch);
   };
   auto block = [&](const std::string& n, int ci, int co, bool dcn, bool down) {
     int cin = ci;
     for (int i = 1; i <= 2; ++i) {
       const std::string cv = n + ".conv" + std::to_string(i);
       if (dcn) {
-        S.push_back({cv + ".offset_conv.weight", (int64_t)18 * cin * 9});
-        S.push_back({cv + ".offset_conv.bias", 18});
-        S.push_back({cv + ".regular_conv.weight", (int64_t)co * cin * 9});
+        S.add(cv + ".offset_conv.weight", (int64_t)18 * cin * 9);
+        S.add(cv + ".offset_conv.bias", 18);
+        S.add(cv + ".regular_conv.weight", (int64_t)co * cin * 9);
       } else {
-        S.push_back({cv + ".weight", (int64_t)co * cin * 9});
+        S.add(cv + ".weight", (int64_t)co * cin * 9);
       }
       bn(n + ".bn" + std::to_string(i), co);
       cin = co;
     }
     if (down) {
-      S.push_back({n + ".downsample.weight", (int64_t)co * ci});
-      S.push_back({n + ".downsample.bias", co});
+      S.add(n + ".downsample.weight", (int64_t)co * ci);
+      S.add(n + ".downsample.bias", co);
     }
   };
   block("block1", 3, c.c1, false, false);
   block("block2", c.c1, c.c2, false, true);
   block("block3", c.c2, c.c3, true, true);
   block("block4", c.c3, c.c4, true, true);
-  S.push_back({"conv1.weight", (int64_t)dq * c.c1});
-  S.push_back({"conv2.weight", (int64_t)dq * c.c2});
-  S.push_back({"conv3.weight", (int64_t)dq * c.c3});
-  S.push_back({"conv4.weight", (int64_t)dq * c.dim});
-  S.push_back({"score_head.0.weight", (int64_t)8 * c.dim});
-  S.push_back({"score_head.2.weight", 4 * 8 * 9});
-  S.push_back({"score_head.4.weight", 4 * 4 * 9});
-  S.push_back({"score_head.6.weight", 1 * 4 * 9});
-  S.push_back({"desc_head.agg_weights", (int64_t)c.M * c.dim * c.dim});
-  S.push_back({"desc_head.offset_conv.0.weight", (int64_t)C2 * c.dim * 9});
-  S.push_back({"desc_head.offset_conv.0.bias", C2});
-  S.push_back({"desc_head.offset_conv.2.weight", (int64_t)C2 * C2});
-  S.push_back({"desc_head.offset_conv.2.bias", C2});
-  S.push_back({"desc_head.sf_conv.weight", (int64_t)c.dim * c.dim});
+  S.add("conv1.weight", (int64_t)dq * c.c1);
+  S.add("conv2.weight", (int64_t)dq * c.c2);
+  S.add("conv3.weight", (int64_t)dq * c.c3);
+  S.add("conv4.weight", (int64_t)dq * c.dim);
+  S.add("score_head.0.weight", (int64_t)8 * c.dim);
+  S.add("score_head.2.weight", 4 * 8 * 9);
+  S.add("score_head.4.weight", 4 * 4 * 9);
+  S.add("score_head.6.weight", 1 * 4 * 9);
+  S.add("desc_head.agg_weights", (int64_t)c.M * c.dim * c.dim);
+  S.add("desc_head.offset_conv.0.weight", (int64_t)C2 * c.dim * 9);
+  S.add("desc_head.offset_conv.0.bias", C2);
+  S.add("desc_head.offset_conv.2.weight", (int64_t)C2 * C2);
+  S.add("desc_head.offset_conv.2.bias", C2);
+  S.add("desc_head.sf_conv.weight", (int64_t)c.dim * c.dim);
 
   size_t o = 0;
   auto take = [&](size_t n) {
@@ -289,7 +272,7 @@ int sp_aliked_create(const sp_aliked_config_t* cfg, int device, sp_aliked_handle
   if (c.dim != c.c4 || (c.dim != 64 && c.dim != 128)) return fail(LG_E_INVALID, "sp_aliked_create: dim must equal c4: 64 or 128");
   if (c.M != 16 && c.M != 32) return fail(LG_E_INVALID, "sp_aliked_create: M must be 16 or 32");
   if (c.nms_radius < 1 || c.nms_radius > 8) return fail(LG_E_INVALID, "sp_aliked_create: nms_radius must be in 1..8");
-  AK_HIP(hipSetDevice(device));
+  LG_HIP(hipSetDevice(device));
   auto* h = new sp_aliked_handle();
   h->cfg = c;
   h->device = device;
@@ -312,62 +295,48 @@ int sp_aliked_destroy(sp_aliked_handle_t* h) {
   return LG_OK;
 }
 
-int sp_aliked_weight_count(const sp_aliked_handle_t* h) { return h ? (int)h->schema.size() : 0; }
-const char* sp_aliked_weight_name(const sp_aliked_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].name.c_str() : nullptr;
-}
-int64_t sp_aliked_weight_numel(const sp_aliked_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].numel : -1;
-}
+int sp_aliked_weight_count(const sp_aliked_handle_t* h) { return h ? lg::weight_count(h->schema) : 0; }
+const char* sp_aliked_weight_name(const sp_aliked_handle_t* h, int i) { return h ? lg::weight_name(h->schema, i) : nullptr; }
+int64_t sp_aliked_weight_numel(const sp_aliked_handle_t* h, int i) { return h ? lg::weight_numel(h->schema, i) : -1; }
 
 int sp_aliked_load_weights(sp_aliked_handle_t* h, int n, const char* const* names, const float* const* tensors,
                            const int64_t* numels, void* stream) {
   if (!h || !names || !tensors || !numels) return fail(LG_E_INVALID, "sp_aliked_load_weights: null argument");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  AK_HIP(hipSetDevice(h->device));
-  std::map<std::string, const float*> got;
-  std::map<std::string, int64_t> gotn;
-  for (int i = 0; i < n; ++i) {
-    if (!names[i] || !tensors[i]) return fail(LG_E_WEIGHTS, "sp_aliked_load_weights: null tensor");
-    got[names[i]] = tensors[i];
-    gotn[names[i]] = numels[i];
-  }
-  for (const auto& t : h->schema) {
-    auto it = gotn.find(t.name);
-    if (it == gotn.end()) return fail(LG_E_WEIGHTS, "sp_aliked_load_weights: missing " + t.name);
-    if (it->second != t.numel)
-      return fail(LG_E_WEIGHTS, "sp_aliked_load_weights: " + t.name + " has " + std::to_string(it->second) +
-                                    " elements, expected " + std::to_string(t.numel));
-  }
+  LG_HIP(hipSetDevice(h->device));
+  std::vector<int> src;
+  std::string err;
+  if (!h->schema.match(n, names, tensors, numels, src, err)) return fail(LG_E_WEIGHTS, err);
+  auto got = [&](const std::string& name) { return tensors[src[h->schema.find(name)]]; };
   h->loaded = false;
   float* G = h->gbuf;
   for (const auto& l : h->layers) {
     const int kk = (l.kind == K_BN3 || l.kind == K_BIAS3 || l.kind == K_PLAIN3) ? 9 : 1;
     const int CoP = lg::ak_copad(l.cout);
-    const float* w = got[l.conv + ".weight"];
+    const float* w = got(l.conv + ".weight");
     if (l.kind == K_BN3) {
-      AK_HIP(lg::sp_bn_fold(got[l.bn + ".weight"], got[l.bn + ".bias"], got[l.bn + ".running_mean"],
-                            got[l.bn + ".running_var"], l.cout, kBnEps, G + h->tmp_s, G + h->tmp_t, nullptr, st));
-      AK_HIP(lg::ak_repack(w, l.cout, l.cin, kk, l.cin * kk, 0, G + h->tmp_s, G + l.w, st));
-      AK_HIP(lg::ak_pad_vec(G + h->tmp_t, l.cout, CoP, G + l.b, st));
+      LG_HIP(lg::sp_bn_fold(got(l.bn + ".weight"), got(l.bn + ".bias"), got(l.bn + ".running_mean"),
+                            got(l.bn + ".running_var"), l.cout, kBnEps, G + h->tmp_s, G + h->tmp_t, nullptr, st));
+      LG_HIP(lg::ak_repack(w, l.cout, l.cin, kk, l.cin * kk, 0, G + h->tmp_s, G + l.w, st));
+      LG_HIP(lg::ak_pad_vec(G + h->tmp_t, l.cout, CoP, G + l.b, st));
     } else if (l.kind == K_SLICE1) {
-      AK_HIP(lg::ak_repack(w, l.cout, l.cin, 1, 4 * l.cin, l.slice, nullptr, G + l.w, st));
-      AK_HIP(lg::ak_pad_vec(nullptr, 0, CoP, G + l.b, st));
+      LG_HIP(lg::ak_repack(w, l.cout, l.cin, 1, 4 * l.cin, l.slice, nullptr, G + l.w, st));
+      LG_HIP(lg::ak_pad_vec(nullptr, 0, CoP, G + l.b, st));
     } else {
-      AK_HIP(lg::ak_repack(w, l.cout, l.cin, kk, l.cin * kk, 0, nullptr, G + l.w, st));
+      LG_HIP(lg::ak_repack(w, l.cout, l.cin, kk, l.cin * kk, 0, nullptr, G + l.w, st));
       const bool has_bias = l.kind == K_BIAS3 || l.kind == K_BIAS1;
-      AK_HIP(lg::ak_pad_vec(has_bias ? got[l.conv + ".bias"] : nullptr, l.cout, CoP, G + l.b, st));
+      LG_HIP(lg::ak_pad_vec(has_bias ? got(l.conv + ".bias") : nullptr, l.cout, CoP, G + l.b, st));
     }
   }
   const auto& c = h->cfg;
   const int C2 = 2 * c.M;
-  AK_HIP(lg::ak_repack(got["desc_head.offset_conv.0.weight"], C2, c.dim, 9, c.dim * 9, 0, nullptr, G + h->w0t, st));
-  AK_HIP(lg::ak_pad_vec(got["desc_head.offset_conv.0.bias"], C2, C2, G + h->b0, st));
-  AK_HIP(lg::ak_repack(got["desc_head.offset_conv.2.weight"], C2, C2, 1, C2, 0, nullptr, G + h->w1t, st));
-  AK_HIP(lg::ak_pad_vec(got["desc_head.offset_conv.2.bias"], C2, C2, G + h->b1, st));
-  AK_HIP(hipMemcpyAsync(G + h->sf, got["desc_head.sf_conv.weight"], (size_t)c.dim * c.dim * sizeof(float),
+  LG_HIP(lg::ak_repack(got("desc_head.offset_conv.0.weight"), C2, c.dim, 9, c.dim * 9, 0, nullptr, G + h->w0t, st));
+  LG_HIP(lg::ak_pad_vec(got("desc_head.offset_conv.0.bias"), C2, C2, G + h->b0, st));
+  LG_HIP(lg::ak_repack(got("desc_head.offset_conv.2.weight"), C2, C2, 1, C2, 0, nullptr, G + h->w1t, st));
+  LG_HIP(lg::ak_pad_vec(got("desc_head.offset_conv.2.bias"), C2, C2, G + h->b1, st));
+  LG_HIP(hipMemcpyAsync(G + h->sf, got("desc_head.sf_conv.weight"), (size_t)c.dim * c.dim * sizeof(float),
                         hipMemcpyDeviceToDevice, st));
-  AK_HIP(lg::ak_agg_transpose(got["desc_head.agg_weights"], c.M, c.dim, G + h->aggT, st));
+  LG_HIP(lg::ak_agg_transpose(got("desc_head.agg_weights"), c.M, c.dim, G + h->aggT, st));
   h->loaded = true;
   return LG_OK;
 }
@@ -393,7 +362,7 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
   const Work w = carve(static_cast<char*>(workspace), c, g);
   if (workspace_bytes < w.bytes) return fail(LG_E_WORKSPACE, "sp_aliked_forward: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  AK_HIP(hipSetDevice(h->device));
+  LG_HIP(hipSetDevice(h->device));
   const float* G = h->gbuf;
   const auto& L = h->layers;
   const int B = g.B;
@@ -406,7 +375,7 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
     }
     return hipEventRecord(h->ev[i], st);
   };
-  AK_HIP(mark(0));
+  LG_HIP(mark(0));
 
   auto conv3 = [&](int li, const float* X, int lvl, const float* res, int act, float* Y) {
     lg::AkConvArgs a{};
@@ -439,34 +408,34 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
     a.srcW = g.W;
     a.pt = g.pt;
     a.pl = g.pl;
-    AK_HIP(lg::ak_conv3x3(a, st));
+    LG_HIP(lg::ak_conv3x3(a, st));
   }
-  AK_HIP(lg::ak_conv3x3(conv3(L_B1C2, w.t1a, 0, nullptr, lg::AK_SELU, w.x1), st));
-  AK_HIP(lg::ak_avgpool(w.x1, (long long)B * c.c1, g.h[0], g.w[0], 2, w.p2, st));
-  AK_HIP(conv1(L_B2D, w.p2, 1, lg::AK_NONE, w.d2));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B2C1, w.p2, 1, nullptr, lg::AK_SELU, w.t2), st));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B2C2, w.t2, 1, w.d2, lg::AK_SELU, w.x2), st));
-  AK_HIP(lg::ak_avgpool(w.x2, (long long)B * c.c2, g.h[1], g.w[1], 4, w.p3, st));
-  AK_HIP(mark(1));
-  AK_HIP(conv1(L_B3D, w.p3, 2, lg::AK_NONE, w.d3));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B3O1, w.p3, 2, nullptr, lg::AK_CLAMP, w.off), st));
-  AK_HIP(deform(L_B3R1, w.p3, 2, nullptr, w.t3));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B3O2, w.t3, 2, nullptr, lg::AK_CLAMP, w.off), st));
-  AK_HIP(deform(L_B3R2, w.t3, 2, w.d3, w.x3));
-  AK_HIP(lg::ak_avgpool(w.x3, (long long)B * c.c3, g.h[2], g.w[2], 4, w.p4, st));
-  AK_HIP(conv1(L_B4D, w.p4, 3, lg::AK_NONE, w.d4));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B4O1, w.p4, 3, nullptr, lg::AK_CLAMP, w.off), st));
-  AK_HIP(deform(L_B4R1, w.p4, 3, nullptr, w.t4));
-  AK_HIP(lg::ak_conv3x3(conv3(L_B4O2, w.t4, 3, nullptr, lg::AK_CLAMP, w.off), st));
-  AK_HIP(deform(L_B4R2, w.t4, 3, w.d4, w.x4));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B1C2, w.t1a, 0, nullptr, lg::AK_SELU, w.x1), st));
+  LG_HIP(lg::ak_avgpool(w.x1, (long long)B * c.c1, g.h[0], g.w[0], 2, w.p2, st));
+  LG_HIP(conv1(L_B2D, w.p2, 1, lg::AK_NONE, w.d2));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B2C1, w.p2, 1, nullptr, lg::AK_SELU, w.t2), st));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B2C2, w.t2, 1, w.d2, lg::AK_SELU, w.x2), st));
+  LG_HIP(lg::ak_avgpool(w.x2, (long long)B * c.c2, g.h[1], g.w[1], 4, w.p3, st));
+  LG_HIP(mark(1));
+  LG_HIP(conv1(L_B3D, w.p3, 2, lg::AK_NONE, w.d3));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B3O1, w.p3, 2, nullptr, lg::AK_CLAMP, w.off), st));
+  LG_HIP(deform(L_B3R1, w.p3, 2, nullptr, w.t3));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B3O2, w.t3, 2, nullptr, lg::AK_CLAMP, w.off), st));
+  LG_HIP(deform(L_B3R2, w.t3, 2, w.d3, w.x3));
+  LG_HIP(lg::ak_avgpool(w.x3, (long long)B * c.c3, g.h[2], g.w[2], 4, w.p4, st));
+  LG_HIP(conv1(L_B4D, w.p4, 3, lg::AK_NONE, w.d4));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B4O1, w.p4, 3, nullptr, lg::AK_CLAMP, w.off), st));
+  LG_HIP(deform(L_B4R1, w.p4, 3, nullptr, w.t4));
+  LG_HIP(lg::ak_conv3x3(conv3(L_B4O2, w.t4, 3, nullptr, lg::AK_CLAMP, w.off), st));
+  LG_HIP(deform(L_B4R2, w.t4, 3, w.d4, w.x4));
 
-  AK_HIP(mark(2));
+  LG_HIP(mark(2));
   // ---- aggregation and score head on the pyramid levels (aliked.py:747-757)
   const float* xs[4] = {w.x1, w.x2, w.x3, w.x4};
   lg::AkPyramid py{};
   py.dq = c.dim / 4;
   for (int l = 0; l < 4; ++l) {
-    AK_HIP(lg::ak_agg(xs[l], B, L[L_AG1 + l].cin, py.dq, (long long)g.hw[l], G + L[L_AG1 + l].w, G + L[L_SP1 + l].w, w.A[l],
+    LG_HIP(lg::ak_agg(xs[l], B, L[L_AG1 + l].cin, py.dq, (long long)g.hw[l], G + L[L_AG1 + l].w, G + L[L_SP1 + l].w, w.A[l],
                       w.P[l], st));
     py.A[l] = w.A[l];
     py.P[l] = w.P[l];
@@ -475,52 +444,52 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
     py.ry[l] = g.Hp > 1 ? (float)(g.h[l] - 1) / (float)(g.Hp - 1) : 0.f;
     py.rx[l] = g.Wp > 1 ? (float)(g.w[l] - 1) / (float)(g.Wp - 1) : 0.f;
   }
-  AK_HIP(lg::ak_head(py, B, w.S8, w.inv, st));
-  AK_HIP(lg::ak_conv3x3(conv3(L_S2, w.S8, 0, nullptr, lg::AK_SELU, w.s4a), st));
-  AK_HIP(lg::ak_conv3x3(conv3(L_S4, w.s4a, 0, nullptr, lg::AK_SELU, w.s4b), st));
+  LG_HIP(lg::ak_head(py, B, w.S8, w.inv, st));
+  LG_HIP(lg::ak_conv3x3(conv3(L_S2, w.S8, 0, nullptr, lg::AK_SELU, w.s4a), st));
+  LG_HIP(lg::ak_conv3x3(conv3(L_S4, w.s4a, 0, nullptr, lg::AK_SELU, w.s4b), st));
   {
     lg::AkConvArgs a = conv3(L_S6, w.s4b, 0, nullptr, lg::AK_SIGMOID, out->score_map);  // unpadded
     a.outH = g.H;
     a.outW = g.W;
     a.oy0 = g.pt;
     a.ox0 = g.pl;
-    AK_HIP(lg::ak_conv3x3(a, st));
+    LG_HIP(lg::ak_conv3x3(a, st));
   }
 
-  AK_HIP(mark(3));
+  LG_HIP(mark(3));
   // ---- DKD (aliked.py:118-216)
   const int H = g.H, W = g.W, cap = g.cap, r = c.nms_radius;
   const size_t HW = (size_t)H * W;
   const float* scores = out->score_map;
-  AK_HIP(lg::sp_nms(scores, B, H, W, r, w.mask, w.sup, w.ss, st));
-  AK_HIP(lg::ak_border_mask(w.mask, B, H, W, r, in->image_size, w.mask2, st));
+  LG_HIP(lg::sp_nms(scores, B, H, W, r, w.mask, w.sup, w.ss, st));
+  LG_HIP(lg::ak_border_mask(w.mask, B, H, W, r, in->image_size, w.mask2, st));
   std::vector<int> hc(B, 0);
   if (topk_mode(c)) {
     const int k = c.max_num_keypoints;
-    AK_HIP(lg::sp_candidates(scores, w.mask2, B, H, W, 0, nullptr, 0.f, w.key, w.idx, w.blk, w.cnt, st));
-    AK_HIP(lg::ak_fill_zeros(scores, w.mask2, B, H, W, k, w.key, w.idx, w.cnt, st));
-    AK_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, (int)HW, k, w.sel_idx, w.sel_score, cap, w.nsel, st));
+    LG_HIP(lg::sp_candidates(scores, w.mask2, B, H, W, 0, nullptr, 0.f, w.key, w.idx, w.blk, w.cnt, st));
+    LG_HIP(lg::ak_fill_zeros(scores, w.mask2, B, H, W, k, w.key, w.idx, w.cnt, st));
+    LG_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, (int)HW, k, w.sel_idx, w.sel_score, cap, w.nsel, st));
   } else {
     bool use_mean = !(c.detection_threshold > 0.f);
     if (!use_mean) {
-      AK_HIP(lg::sp_candidates(scores, w.mask2, B, H, W, 0, nullptr, c.detection_threshold, w.key, w.idx, w.blk, w.cnt, st));
-      AK_HIP(hipMemcpyAsync(hc.data(), w.cnt, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      AK_HIP(hipStreamSynchronize(st));
+      LG_HIP(lg::sp_candidates(scores, w.mask2, B, H, W, 0, nullptr, c.detection_threshold, w.key, w.idx, w.blk, w.cnt, st));
+      LG_HIP(hipMemcpyAsync(hc.data(), w.cnt, B * sizeof(int), hipMemcpyDeviceToHost, st));
+      LG_HIP(hipStreamSynchronize(st));
       long long total = 0;
       for (int v : hc) total += v;
       use_mean = total == 0;  // aliked.py:141-143: nothing passes in the whole batch
     }
     if (use_mean) {
       std::vector<float> hm(B);
-      AK_HIP(lg::ak_mean(scores, B, (long long)HW, w.mean, st));
-      AK_HIP(hipMemcpyAsync(hm.data(), w.mean, B * sizeof(float), hipMemcpyDeviceToHost, st));
-      AK_HIP(hipStreamSynchronize(st));
+      LG_HIP(lg::ak_mean(scores, B, (long long)HW, w.mean, st));
+      LG_HIP(hipMemcpyAsync(hm.data(), w.mean, B * sizeof(float), hipMemcpyDeviceToHost, st));
+      LG_HIP(hipStreamSynchronize(st));
       const int nb = lg::sp_cand_blocks(H);
       for (int b = 0; b < B; ++b)
-        AK_HIP(lg::sp_candidates(scores + b * HW, w.mask2 + b * HW, 1, H, W, 0, nullptr, hm[b], w.key + b * HW, w.idx + b * HW,
+        LG_HIP(lg::sp_candidates(scores + b * HW, w.mask2 + b * HW, 1, H, W, 0, nullptr, hm[b], w.key + b * HW, w.idx + b * HW,
                                  w.blk + (size_t)b * nb, w.cnt + b, st));
-      AK_HIP(hipMemcpyAsync(hc.data(), w.cnt, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      AK_HIP(hipStreamSynchronize(st));
+      LG_HIP(hipMemcpyAsync(hc.data(), w.cnt, B * sizeof(int), hipMemcpyDeviceToHost, st));
+      LG_HIP(hipStreamSynchronize(st));
     }
     const int nl = n_limit(c);
     const int mx = *std::max_element(hc.begin(), hc.end());
@@ -530,12 +499,12 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
       k = nl;
     }
     if (std::min(mx, nl) > cap) return fail(LG_E_INVALID, "sp_aliked_forward: capacity below the keypoint count");
-    AK_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, (int)HW, k, w.sel_idx, w.sel_score, cap, w.nsel, st));
+    LG_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, (int)HW, k, w.sel_idx, w.sel_score, cap, w.nsel, st));
     for (int b = 0; b < B; ++b) hc[b] = std::min(hc[b], nl);
   }
-  AK_HIP(lg::ak_refine(scores, w.sel_idx, w.nsel, B, cap, H, W, r, w.kn, out->keypoints, out->sampled_scores, out->dispersity,
+  LG_HIP(lg::ak_refine(scores, w.sel_idx, w.nsel, B, cap, H, W, r, w.kn, out->keypoints, out->sampled_scores, out->dispersity,
                        st));
-  AK_HIP(hipMemcpyAsync(out->counts, w.nsel, B * sizeof(int), hipMemcpyDeviceToDevice, st));
+  LG_HIP(hipMemcpyAsync(out->counts, w.nsel, B * sizeof(int), hipMemcpyDeviceToDevice, st));
   if (out->host_counts) {
     if (topk_mode(c))
       for (int b = 0; b < B; ++b) out->host_counts[b] = c.max_num_keypoints;
@@ -543,7 +512,7 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
       for (int b = 0; b < B; ++b) out->host_counts[b] = hc[b];
   }
 
-  AK_HIP(mark(4));
+  LG_HIP(mark(4));
   // ---- SDDH (aliked.py:513-588)
   lg::AkSddh s{};
   s.py = py;
@@ -557,8 +526,8 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
   s.dim = c.dim;
   s.M = c.M;
   s.kn = w.kn;
-  AK_HIP(lg::ak_sddh_offsets(s, G + h->w0t, G + h->b0, G + h->w1t, G + h->b1, w.offs, st));
-  AK_HIP(lg::ak_sddh_sample(s, w.offs, w.F, st));
+  LG_HIP(lg::ak_sddh_offsets(s, G + h->w0t, G + h->b0, G + h->w1t, G + h->b1, w.offs, st));
+  LG_HIP(lg::ak_sddh_sample(s, w.offs, w.F, st));
   const long long rows = (long long)B * cap * c.M;
   {  // sf_conv: [N M, dim] x [dim, dim] on the matrix cores (bf16x6: fp32-accurate products)
     lg::GemmArgs a{};
@@ -572,9 +541,9 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
     a.out_scale = 1.f;
     a.R = (int)rows;
     a.Nout = c.dim;
-    AK_HIP(lg::gemm_x6(a, lg::EPI_STORE, 1, st));
+    LG_HIP(lg::gemm_x6(a, lg::EPI_STORE, 1, st));
   }
-  AK_HIP(lg::ak_selu(w.Y1, rows * c.dim, st));
+  LG_HIP(lg::ak_selu(w.Y1, rows * c.dim, st));
   {  // einsum("ncp,pcd->nd"): [N, M dim] x [M dim, dim]
     lg::GemmArgs a{};
     a.A0 = w.Y1;
@@ -587,10 +556,10 @@ int sp_aliked_forward(sp_aliked_handle_t* h, const sp_aliked_inputs_t* in, sp_al
     a.out_scale = 1.f;
     a.R = B * cap;
     a.Nout = c.dim;
-    AK_HIP(lg::gemm_x6(a, lg::EPI_STORE, 1, st));
+    LG_HIP(lg::gemm_x6(a, lg::EPI_STORE, 1, st));
   }
-  AK_HIP(lg::ak_l2norm(w.D, (long long)B * cap, c.dim, out->descriptors, st));
-  AK_HIP(mark(5));
+  LG_HIP(lg::ak_l2norm(w.D, (long long)B * cap, c.dim, out->descriptors, st));
+  LG_HIP(mark(5));
   h->ev_valid = h->profile;
   return LG_OK;
 }
@@ -605,8 +574,8 @@ int sp_aliked_set_profile(sp_aliked_handle_t* h, int32_t on) {
 int sp_aliked_stage_ms(sp_aliked_handle_t* h, float* ms) {
   if (!h || !ms) return fail(LG_E_INVALID, "sp_aliked_stage_ms: null argument");
   if (!h->ev_valid) return fail(LG_E_INVALID, "sp_aliked_stage_ms: no profiled forward (sp_aliked_set_profile)");
-  AK_HIP(hipEventSynchronize(h->ev[5]));
-  for (int i = 0; i < 5; ++i) AK_HIP(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
+  LG_HIP(hipEventSynchronize(h->ev[5]));
+  for (int i = 0; i < 5; ++i) LG_HIP(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
   return LG_OK;
 }
 
@@ -621,9 +590,9 @@ int sp_aliked_deform_conv(const float* x, const float* offset, const float* weig
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* wt = scratch;
   float* bp = scratch + (size_t)9 * Cin * Cout;
-  AK_HIP(lg::ak_repack(weight, Cout, Cin, 9, Cin * 9, 0, nullptr, wt, st));
-  AK_HIP(lg::ak_pad_vec(bias, Cout, Cout, bp, st));
-  AK_HIP(lg::ak_deform_conv(x, offset, B, Cin, Cout, H, W, wt, bp, nullptr, lg::AK_NONE, y, st));
+  LG_HIP(lg::ak_repack(weight, Cout, Cin, 9, Cin * 9, 0, nullptr, wt, st));
+  LG_HIP(lg::ak_pad_vec(bias, Cout, Cout, bp, st));
+  LG_HIP(lg::ak_deform_conv(x, offset, B, Cin, Cout, H, W, wt, bp, nullptr, lg::AK_NONE, y, st));
   return LG_OK;
 }
 

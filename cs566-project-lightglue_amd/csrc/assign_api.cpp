@@ -15,24 +15,13 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
 #include "common.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
 using namespace lg;
-
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define ASG_HIP(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int kD = 256;
 constexpr int kSlots = 2;  // 0: max|md|; 1: the image's exponent
@@ -176,14 +165,14 @@ int lg_assign(lg_assign_args_t* args, void* workspace, size_t workspace_bytes, v
 
   if (a.Mb) {
     hipLaunchKernelGGL(assign_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, a.Mb, a.Nb, B, M, N, a.raw_counts, cnt);
-    ASG_HIP(hipGetLastError());
+    LG_HIP(hipGetLastError());
   }
   if (a.poison) {
-    ASG_HIP(fill_f32(a.la, LG_ASSIGN_SENTINEL_F, (size_t)B * (M + 1) * (N + 1), st));
-    ASG_HIP(fill_f32(a.s0, LG_ASSIGN_SENTINEL_F, (size_t)B * M, st));
-    ASG_HIP(fill_f32(a.s1, LG_ASSIGN_SENTINEL_F, (size_t)B * N, st));
-    ASG_HIP(fill_i64(a.m0, LG_ASSIGN_SENTINEL_I, (size_t)B * M, st));
-    ASG_HIP(fill_i64(a.m1, LG_ASSIGN_SENTINEL_I, (size_t)B * N, st));
+    LG_HIP(fill_f32(a.la, LG_ASSIGN_SENTINEL_F, (size_t)B * (M + 1) * (N + 1), st));
+    LG_HIP(fill_f32(a.s0, LG_ASSIGN_SENTINEL_F, (size_t)B * M, st));
+    LG_HIP(fill_f32(a.s1, LG_ASSIGN_SENTINEL_F, (size_t)B * N, st));
+    LG_HIP(fill_i64(a.m0, LG_ASSIGN_SENTINEL_I, (size_t)B * M, st));
+    LG_HIP(fill_i64(a.m1, LG_ASSIGN_SENTINEL_I, (size_t)B * N, st));
   }
 
   AssignArgs aa;
@@ -198,24 +187,24 @@ int lg_assign(lg_assign_args_t* args, void* workspace, size_t workspace_bytes, v
   }
 
   if (a.route == LG_ASSIGN_RECOMPUTED) {
-    ASG_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
-    ASG_HIP(hipMemsetAsync(planes, 0, (size_t)2 * L.rows_pad * kD * 2, st));
-    ASG_HIP(range_absmax2(a.md0, (size_t)B * M * kD, a.md1, (size_t)B * N * kD, rtab, 0, st));
+    LG_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
+    LG_HIP(hipMemsetAsync(planes, 0, (size_t)2 * L.rows_pad * kD * 2, st));
+    LG_HIP(range_absmax2(a.md0, (size_t)B * M * kD, a.md1, (size_t)B * N * kD, rtab, 0, st));
     // the final_proj epilogue's RangeOut (lightglue_api.cpp: track 0, lshift 11), its bound measured
-    ASG_HIP(rows_to_planes2(a.md0, B * M, a.md1, B * N, kD, kD, planes, L.rows_pad, 0,
-                            RangeOut{rtab, 0, -1, 1.f, 0.f, 0.f, 1, 0, 11}, st));
+    LG_HIP(rows_to_planes2(a.md0, B * M, a.md1, B * N, kD, kD, planes, L.rows_pad, 0,
+                           RangeOut{rtab, 0, -1, 1.f, 0.f, 0.f, 1, 0, 11}, st));
     if (a.poison) {
       const size_t n = (size_t)L.rows_pad * kD;
       hipLaunchKernelGGL(assign_poison_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                          reinterpret_cast<unsigned short*>(planes), ps, L.rows_pad, B, M, N, a.Mb ? cnt : nullptr);
-      ASG_HIP(hipGetLastError());
+      LG_HIP(hipGetLastError());
     }
     const hipError_t e = assign_and_filter_h3(aa, PlaneRef{planes, ps, L.rows_pad}, rtab, 1, st);
     if (e == hipErrorInvalidValue) return fail(LG_E_INVALID, "assign_and_filter_h3 takes no such operands (LG_ASSIGN_SIM_X6 set?)");
-    ASG_HIP(e);
+    LG_HIP(e);
     unsigned htab[kSlots * kRangeStride];
-    ASG_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
-    ASG_HIP(hipStreamSynchronize(st));
+    LG_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
+    LG_HIP(hipStreamSynchronize(st));
     a.exp_md = (int)htab[kRangeStride + kRangeShards];
     for (int i = 0; i < kRangeShards; ++i) {
       float v;
@@ -235,16 +224,16 @@ int lg_assign(lg_assign_args_t* args, void* workspace, size_t workspace_bytes, v
     g.A0 = a.md0; g.lda0 = kD; g.K0 = kD; g.K = kD; g.sA = (long long)M * kD;
     g.W = a.md1; g.ldw = kD; g.sW = (long long)N * kD;
     g.R = M; g.Nout = N; g.Y = simbuf; g.ldy = N; g.sY = (long long)M * N;
-    ASG_HIP(gemm_x6(g, EPI_STORE, B, st));
+    LG_HIP(gemm_x6(g, EPI_STORE, B, st));
     if (a.poison && a.Mb) {
       const size_t n = (size_t)B * M * N;
       hipLaunchKernelGGL(assign_poison_sim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, simbuf, B, M, N, cnt);
-      ASG_HIP(hipGetLastError());
+      LG_HIP(hipGetLastError());
     }
     aa.sim = simbuf;
   }
-  ASG_HIP(assign_and_filter(aa, st));
-  ASG_HIP(hipStreamSynchronize(st));
+  LG_HIP(assign_and_filter(aa, st));
+  LG_HIP(hipStreamSynchronize(st));
   return LG_OK;
 }
 

@@ -6,15 +6,10 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
 // launch-grid and flat-index limits of gt_match.hip / gt_depth.hip
 bool shape_ok(int64_t B, int64_t M, int64_t N) {
   const int64_t lim = 0x7fffffffLL;

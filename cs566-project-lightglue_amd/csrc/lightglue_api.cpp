@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
 #include "common.h"
@@ -20,34 +21,16 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define LG_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                     \
-  } while (0)
-
-struct Tensor {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t numel() const {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    return n;
-  }
-};
-
 // Same order as lightglue_amd.weights.state_dict_schema (lightglue.py:367-398).
-std::vector<Tensor> make_schema(const lg_config_t& c) {
+lg::WeightSchema make_schema(const lg_config_t& c) {
   const int64_t d = c.descriptor_dim, din = c.input_dim, L = c.n_layers;
   const int64_t hd = d / c.num_heads, m_in = 2 + 2 * (c.add_scale_ori ? 1 : 0);
-  std::vector<Tensor> s;
-  auto add = [&](const std::string& n, std::vector<int64_t> sh) { s.push_back({n, sh}); };
+  lg::WeightSchema s;
+  auto add = [&](const std::string& n, std::initializer_list<int64_t> shape) {
+    int64_t numel = 1;
+    for (int64_t v : shape) numel *= v;
+    s.add(n, numel);
+  };
   auto ffn = [&](const std::string& p) {
     add(p + ".ffn.0.weight", {2 * d, 2 * d});
     add(p + ".ffn.0.bias", {2 * d});
@@ -113,7 +96,7 @@ size_t align64(size_t n) { return (n + 63) & ~size_t(63); }
 }  // namespace
 
 namespace lg {
-// the other C-ABI families of this library (superpoint_api.cpp) report through lg_last_error()
+// every C-ABI family of this library reports through lg_last_error() (api_common.h: fail)
 int api_fail(int code, const char* msg) {
   g_err = msg;
   return code;
@@ -125,8 +108,7 @@ struct lg_handle {
   int device;
   lg_grad_ready_fn grad_hook = nullptr;  // lg_set_grad_ready_hook (data-parallel training)
   void* grad_hook_ctx = nullptr;
-  std::vector<Tensor> schema;
-  std::map<std::string, int> index;
+  lg::WeightSchema schema;
   // where each schema tensor goes: destination offset (floats) and how (0 copy, 1 gather rows
   // through perm[0,768) (Wqkv), 2 gather through perm[768,1024) (to_qk / to_v))
   std::vector<size_t> dst;
@@ -281,8 +263,8 @@ void plan_layout(lg_handle* h) {
   // destination of each schema tensor (projection weights are gathered through head_perm)
   h->dst.assign(h->schema.size(), SIZE_MAX);
   h->gkind.assign(h->schema.size(), 0);
-  for (size_t k = 0; k < h->schema.size(); ++k) {
-    const std::string& n = h->schema[k].name;
+  for (int k = 0; k < h->schema.size(); ++k) {
+    const std::string& n = h->schema.name(k);
     size_t o = SIZE_MAX;
     if (n == "posenc.Wr.weight") o = h->Wr;
     else if (n == "posenc.condition_modulation.weight") o = h->Wc;
@@ -463,11 +445,10 @@ int lg_create(const lg_config_t* cfg, int device, lg_handle_t** out) {
   if (const char* f = getenv("LG_FOLD_OUT_PROJ")) h->fold = atoi(f) != 0;
   if (const char* f = getenv("LG_FFN3_REVERSE")) h->ffn3_reverse = atoi(f) != 0;
   h->schema = make_schema(*cfg);
-  for (size_t k = 0; k < h->schema.size(); ++k) h->index[h->schema[k].name] = (int)k;
   plan_layout(h);
-  for (size_t k = 0; k < h->schema.size(); ++k)
+  for (int k = 0; k < h->schema.size(); ++k)
     if (h->dst[k] == SIZE_MAX) {
-      std::string n = h->schema[k].name;
+      std::string n = h->schema.name(k);
       delete h;
       return fail(LG_E_WEIGHTS, "internal: unplaced schema tensor " + n);
     }
@@ -519,42 +500,26 @@ int handle_device(const lg_handle* h) { return h->device; }
 void handle_grad_ready(const lg_handle* h, int layer, void* stream) {
   if (h->grad_hook) h->grad_hook(h->grad_hook_ctx, layer, stream);
 }
-int handle_weight_index(const lg_handle* h, const std::string& name) {
-  auto it = h->index.find(name);
-  return it == h->index.end() ? -1 : it->second;
-}
+const WeightSchema& handle_schema(const lg_handle* h) { return h->schema; }
 }  // namespace lg
 
 extern "C" {
 
-int lg_weight_count(const lg_handle_t* h) { return h ? (int)h->schema.size() : 0; }
-const char* lg_weight_name(const lg_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].name.c_str() : nullptr;
-}
-int64_t lg_weight_numel(const lg_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].numel() : -1;
-}
+int lg_weight_count(const lg_handle_t* h) { return h ? lg::weight_count(h->schema) : 0; }
+const char* lg_weight_name(const lg_handle_t* h, int i) { return h ? lg::weight_name(h->schema, i) : nullptr; }
+int64_t lg_weight_numel(const lg_handle_t* h, int i) { return h ? lg::weight_numel(h->schema, i) : -1; }
 
 int lg_load_weights(lg_handle_t* h, int n, const char* const* names, const float* const* tensors, const int64_t* numels,
                     void* stream) {
   if (!h || n < 0 || (n && (!names || !tensors || !numels))) return fail(LG_E_INVALID, "null argument");
   LG_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int> seen(h->schema.size(), 0);
+  std::vector<int> src;
+  std::string err;
+  if (!h->schema.match(n, names, tensors, numels, src, err)) return fail(LG_E_WEIGHTS, err);
   for (int i = 0; i < n; ++i) {
-    auto it = h->index.find(names[i]);
-    if (it == h->index.end()) return fail(LG_E_WEIGHTS, std::string("unexpected key in state_dict: ") + names[i]);
-    const int k = it->second;
-    if (seen[k]++) return fail(LG_E_WEIGHTS, std::string("duplicate key: ") + names[i]);
-    if (numels[i] != h->schema[k].numel())
-      return fail(LG_E_WEIGHTS, std::string("size mismatch for ") + names[i] + ": expected " +
-                                    std::to_string(h->schema[k].numel()) + " got " + std::to_string(numels[i]));
-  }
-  for (size_t k = 0; k < h->schema.size(); ++k)
-    if (!seen[k]) return fail(LG_E_WEIGHTS, "missing key in state_dict: " + h->schema[k].name);
-  for (int i = 0; i < n; ++i) {
-    const int k = h->index[names[i]];
-    const std::string& name = h->schema[k].name;
+    const int k = h->schema.find(names[i]);
+    const std::string& name = h->schema.name(k);
     if (h->gkind[k] != 0) {
       const bool is_w = name.size() > 6 && name.compare(name.size() - 6, 6, "weight") == 0;
       const int rows = h->gkind[k] == 1 ? 3 * D : D;

@@ -13,28 +13,20 @@
 #include <vector>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 #include "train.h"
 
 namespace lg {
-int api_fail(int code, const char* msg);
 const lg_config_t* handle_config(const lg_handle* h);
 int handle_device(const lg_handle* h);
 void handle_grad_ready(const lg_handle* h, int layer, void* stream);  // lg_set_grad_ready_hook
-int handle_weight_index(const lg_handle* h, const std::string& name);
+const WeightSchema& handle_schema(const lg_handle* h);
 }  // namespace lg
 
 namespace {
 
 using namespace lg;
-
-int fail(int code, const std::string& msg) { return api_fail(code, msg.c_str()); }
-
-#define TR_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int D = 256;
 
@@ -185,8 +177,8 @@ struct Params {
   const lg_handle_t* h;
   const float* const* p;
   float* const* g;
-  const float* w(const std::string& n) const { return p[handle_weight_index(h, n)]; }
-  float* gr(const std::string& n) const { return g ? g[handle_weight_index(h, n)] : nullptr; }
+  const float* w(const std::string& n) const { return p[handle_schema(h).find(n)]; }
+  float* gr(const std::string& n) const { return g ? g[handle_schema(h).find(n)] : nullptr; }
 };
 
 struct Ctx {
@@ -377,16 +369,16 @@ int lg_train_forward(lg_handle_t* h, const float* const* params, const lg_inputs
   const bool ckpt = (in->flags & LG_FWD_CHECKPOINTED) != 0;
   Saved s = carve_saved((char*)saved, d, ckpt);
   if (saved_bytes < s.bytes) return fail(LG_E_WORKSPACE, "saved buffer too small: need " + std::to_string(s.bytes));
-  TR_HIP(hipSetDevice(handle_device(h)));
+  LG_HIP(hipSetDevice(handle_device(h)));
   const Ctx c{(hipStream_t)stream, nullptr, 0, nullptr};
   const Params P{h, params, nullptr};
   const int B = d.B, M = d.M, N = d.N, R = d.R, R0 = d.R0;
   // positional encoding (lightglue.py:452-456,490-494); no image_size: min/max extent (:25-26)
-  if (in->image_size0) TR_HIP(hipMemcpyAsync(s.SZ, in->image_size0, 2 * B * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-  else TR_HIP(kpt_extent(in->keypoints0, B, M, s.SZ, c.st));
+  if (in->image_size0) LG_HIP(hipMemcpyAsync(s.SZ, in->image_size0, 2 * B * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+  else LG_HIP(kpt_extent(in->keypoints0, B, M, s.SZ, c.st));
   if (in->image_size1)
-    TR_HIP(hipMemcpyAsync(s.SZ + 2 * B, in->image_size1, 2 * B * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-  else TR_HIP(kpt_extent(in->keypoints1, B, N, s.SZ + 2 * B, c.st));
+    LG_HIP(hipMemcpyAsync(s.SZ + 2 * B, in->image_size1, 2 * B * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+  else LG_HIP(kpt_extent(in->keypoints1, B, N, s.SZ + 2 * B, c.st));
   for (int img = 0; img < 2; ++img) {
     TPE p{};
     p.kpts = img ? in->keypoints1 : in->keypoints0;
@@ -403,27 +395,27 @@ int lg_train_forward(lg_handle_t* h, const float* const* params, const lg_inputs
     p.x = s.PEX + r0 * 4;
     p.cosb = s.COS + r0 * 32;
     p.sinb = s.SIN + r0 * 32;
-    TR_HIP(pe_train(p, c.st));
+    LG_HIP(pe_train(p, c.st));
   }
   // input descriptors (input_proj, :370-373,486-487)
   if (d.proj) {
-    TR_HIP(hipMemcpyAsync(s.Din, in->descriptors0, (size_t)R0 * d.din * 4, hipMemcpyDeviceToDevice, c.st));
-    TR_HIP(hipMemcpyAsync(s.Din + (size_t)R0 * d.din, in->descriptors1, (size_t)(R - R0) * d.din * 4,
+    LG_HIP(hipMemcpyAsync(s.Din, in->descriptors0, (size_t)R0 * d.din * 4, hipMemcpyDeviceToDevice, c.st));
+    LG_HIP(hipMemcpyAsync(s.Din + (size_t)R0 * d.din, in->descriptors1, (size_t)(R - R0) * d.din * 4,
                           hipMemcpyDeviceToDevice, c.st));
-    TR_HIP(linear(c, s.Din, d.din, R, d.din, P.w("input_proj.weight"), P.w("input_proj.bias"), D, s.X0, D));
+    LG_HIP(linear(c, s.Din, d.din, R, d.din, P.w("input_proj.weight"), P.w("input_proj.bias"), D, s.X0, D));
   } else {
-    TR_HIP(hipMemcpyAsync(s.X0, in->descriptors0, (size_t)R0 * D * 4, hipMemcpyDeviceToDevice, c.st));
-    TR_HIP(hipMemcpyAsync(s.X0 + (size_t)R0 * D, in->descriptors1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+    LG_HIP(hipMemcpyAsync(s.X0, in->descriptors0, (size_t)R0 * D * 4, hipMemcpyDeviceToDevice, c.st));
+    LG_HIP(hipMemcpyAsync(s.X0 + (size_t)R0 * D, in->descriptors1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   }
   for (int l = 0; l < d.L; ++l) {
-    TR_HIP(layer_forward(c, P, s, d, l));
+    LG_HIP(layer_forward(c, P, s, d, l));
     const Blk& cb = s.cross[l];
     // ref_descriptors*[:, l] (:521-524,572)
     if (layer_descriptors0)
-      TR_HIP(hipMemcpy2DAsync(layer_descriptors0 + (size_t)l * M * D, (size_t)d.L * M * D * 4, cb.Y, (size_t)M * D * 4,
+      LG_HIP(hipMemcpy2DAsync(layer_descriptors0 + (size_t)l * M * D, (size_t)d.L * M * D * 4, cb.Y, (size_t)M * D * 4,
                               (size_t)M * D * 4, B, hipMemcpyDeviceToDevice, c.st));
     if (layer_descriptors1)
-      TR_HIP(hipMemcpy2DAsync(layer_descriptors1 + (size_t)l * N * D, (size_t)d.L * N * D * 4, cb.Y + (size_t)R0 * D,
+      LG_HIP(hipMemcpy2DAsync(layer_descriptors1 + (size_t)l * N * D, (size_t)d.L * N * D * 4, cb.Y + (size_t)R0 * D,
                               (size_t)N * D * 4, (size_t)N * D * 4, B, hipMemcpyDeviceToDevice, c.st));
   }
   return LG_OK;
@@ -441,16 +433,16 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
   if (saved_bytes < s.bytes) return fail(LG_E_WORKSPACE, "saved buffer too small");
   Scratch w = carve_scratch((char*)scratch, d);
   if (scratch_bytes < w.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(w.bytes));
-  TR_HIP(hipSetDevice(handle_device(h)));
+  LG_HIP(hipSetDevice(handle_device(h)));
   const Ctx c{(hipStream_t)stream, w.WS, w.ws_floats, w.PART};
   const Params P{h, params, grads};
   const int B = d.B, M = d.M, N = d.N, R = d.R, R0 = d.R0, H = d.H;
   const float scale = 0.125f;
   const size_t lse1 = (size_t)B * H * M;
   const size_t o1 = (size_t)R0 * D;
-  TR_HIP(hipMemsetAsync(w.GX, 0, (size_t)R * D * 4, c.st));
-  TR_HIP(hipMemsetAsync(w.GCOS, 0, (size_t)R * 32 * 4, c.st));
-  TR_HIP(hipMemsetAsync(w.GSIN, 0, (size_t)R * 32 * 4, c.st));
+  LG_HIP(hipMemsetAsync(w.GX, 0, (size_t)R * D * 4, c.st));
+  LG_HIP(hipMemsetAsync(w.GCOS, 0, (size_t)R * 32 * 4, c.st));
+  LG_HIP(hipMemsetAsync(w.GSIN, 0, (size_t)R * 32 * 4, c.st));
   for (int l = d.L - 1; l >= 0; --l) {
     const std::string sp = "transformers." + std::to_string(l) + ".self_attn";
     const std::string cp = "transformers." + std::to_string(l) + ".cross_attn";
@@ -460,17 +452,17 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
     // checkpointed: recompute layer l's activations from its saved input (torch.utils.checkpoint's
     // recomputation, lightglue.py:515-518); the forward kernels are deterministic, so they are the
     // forward pass's values exactly
-    if (ckpt) TR_HIP(layer_forward(Ctx{c.st, nullptr, 0, nullptr}, P, s, d, l));  // the forward's Ctx: same GEMM splits
+    if (ckpt) LG_HIP(layer_forward(Ctx{c.st, nullptr, 0, nullptr}, P, s, d, l));  // the forward's Ctx: same GEMM splits
     // d/d(layer output) += the heads' gradient of ref_descriptors*[:, l]
-    TR_HIP(add_layer_rows(w.GX, grad_layer_descriptors0, grad_layer_descriptors1, B, M, N, d.L, l, c.st));
+    LG_HIP(add_layer_rows(w.GX, grad_layer_descriptors0, grad_layer_descriptors1, B, M, N, d.L, l, c.st));
     // ---- CrossBlock backward: GX -> GY (d/d self-block output sb.Y)
-    TR_HIP(ffn_backward(c, P, cp, cb, sb.Y, w.GX, w.GY, w, R));
+    LG_HIP(ffn_backward(c, P, cp, cb, sb.Y, w.GX, w.GY, w, R));
     const float* gmsg = w.GC + D;
-    TR_HIP(linear_wgrad(c, gmsg, 2 * D, cb.O, D, R, D, D, P.gr(cp + ".to_out.weight"), P.gr(cp + ".to_out.bias")));
-    TR_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, P.w(cp + ".to_out.weight"), D, w.GO, D));
-    TR_HIP(attn_delta(cb.O, w.GO, D, B, H, M, w.DELTA, c.st));
-    TR_HIP(attn_delta(cb.O + o1, w.GO + o1, D, B, H, N, w.DELTA + lse1, c.st));
-    TR_HIP(hipMemsetAsync(w.GQ + o1, 0, (size_t)(R - R0) * D * 4, c.st));
+    LG_HIP(linear_wgrad(c, gmsg, 2 * D, cb.O, D, R, D, D, P.gr(cp + ".to_out.weight"), P.gr(cp + ".to_out.bias")));
+    LG_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, P.w(cp + ".to_out.weight"), D, w.GO, D));
+    LG_HIP(attn_delta(cb.O, w.GO, D, B, H, M, w.DELTA, c.st));
+    LG_HIP(attn_delta(cb.O + o1, w.GO + o1, D, B, H, N, w.DELTA + lse1, c.st));
+    LG_HIP(hipMemsetAsync(w.GQ + o1, 0, (size_t)(R - R0) * D * 4, c.st));
     {  // path 1 (image-1 queries over image-0 keys): dQ -> gqk1 (atomics), dK -> gqk0, dV -> gv0
       TAttn a = attn_args(cb.Q + o1, cb.Q, cb.V, cb.O + o1, cb.LSE + lse1, B, H, N, M, scale);
       a.dO = w.GO + o1;
@@ -479,7 +471,7 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
       a.dK = w.GQ;
       a.dV = w.GV;
       a.accum_kv = 0;
-      TR_HIP(tattn_backward(a, c.st));
+      LG_HIP(tattn_backward(a, c.st));
     }
     {  // path 0 (image-0 queries over image-1 keys): dQ -> gqk0 (+= onto path 1's dK), dK += gqk1
       TAttn a = attn_args(cb.Q, cb.Q + o1, cb.V + o1, cb.O, cb.LSE, B, H, M, N, scale);
@@ -489,20 +481,20 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
       a.dK = w.GQ + o1;
       a.dV = w.GV + o1;
       a.accum_kv = 1;
-      TR_HIP(hipMemsetAsync(w.GV + o1, 0, (size_t)(R - R0) * D * 4, c.st));
-      TR_HIP(tattn_backward(a, c.st));
+      LG_HIP(hipMemsetAsync(w.GV + o1, 0, (size_t)(R - R0) * D * 4, c.st));
+      LG_HIP(tattn_backward(a, c.st));
     }
-    TR_HIP(linear_wgrad(c, w.GQ, D, sb.Y, D, R, D, D, P.gr(cp + ".to_qk.weight"), P.gr(cp + ".to_qk.bias")));
-    TR_HIP(linear_wgrad(c, w.GV, D, sb.Y, D, R, D, D, P.gr(cp + ".to_v.weight"), P.gr(cp + ".to_v.bias")));
-    TR_HIP(linear_dgrad(c, w.GQ, D, R, D, P.w(cp + ".to_qk.weight"), D, w.GY, D, 1.f));
-    TR_HIP(linear_dgrad(c, w.GV, D, R, D, P.w(cp + ".to_v.weight"), D, w.GY, D, 1.f));
+    LG_HIP(linear_wgrad(c, w.GQ, D, sb.Y, D, R, D, D, P.gr(cp + ".to_qk.weight"), P.gr(cp + ".to_qk.bias")));
+    LG_HIP(linear_wgrad(c, w.GV, D, sb.Y, D, R, D, D, P.gr(cp + ".to_v.weight"), P.gr(cp + ".to_v.bias")));
+    LG_HIP(linear_dgrad(c, w.GQ, D, R, D, P.w(cp + ".to_qk.weight"), D, w.GY, D, 1.f));
+    LG_HIP(linear_dgrad(c, w.GV, D, R, D, P.w(cp + ".to_v.weight"), D, w.GY, D, 1.f));
     // ---- SelfBlock backward: GY -> GX (d/d layer input X)
-    TR_HIP(ffn_backward(c, P, sp, sb, X, w.GY, w.GX, w, R));
-    TR_HIP(linear_wgrad(c, gmsg, 2 * D, sb.O, D, R, D, D, P.gr(sp + ".out_proj.weight"), P.gr(sp + ".out_proj.bias")));
-    TR_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, P.w(sp + ".out_proj.weight"), D, w.GO, D));
-    TR_HIP(attn_delta(sb.O, w.GO, D, B, H, M, w.DELTA, c.st));
-    TR_HIP(attn_delta(sb.O + o1, w.GO + o1, D, B, H, N, w.DELTA + lse1, c.st));
-    TR_HIP(hipMemsetAsync(w.GQ, 0, (size_t)R * D * 4, c.st));
+    LG_HIP(ffn_backward(c, P, sp, sb, X, w.GY, w.GX, w, R));
+    LG_HIP(linear_wgrad(c, gmsg, 2 * D, sb.O, D, R, D, D, P.gr(sp + ".out_proj.weight"), P.gr(sp + ".out_proj.bias")));
+    LG_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, P.w(sp + ".out_proj.weight"), D, w.GO, D));
+    LG_HIP(attn_delta(sb.O, w.GO, D, B, H, M, w.DELTA, c.st));
+    LG_HIP(attn_delta(sb.O + o1, w.GO + o1, D, B, H, N, w.DELTA + lse1, c.st));
+    LG_HIP(hipMemsetAsync(w.GQ, 0, (size_t)R * D * 4, c.st));
     for (int img = 0; img < 2; ++img) {
       const size_t off = img ? o1 : 0;
       const int n = img ? N : M;
@@ -512,23 +504,23 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
       a.dQ = w.GQ + off;
       a.dK = w.GK + off;
       a.dV = w.GV + off;
-      TR_HIP(tattn_backward(a, c.st));
+      LG_HIP(tattn_backward(a, c.st));
     }
-    TR_HIP(rotary_split_bwd(w.GQ, w.GK, w.GV, sb.Q, sb.K, s.COS, s.SIN, R, H, w.GQKV, w.GCOS, w.GSIN, c.st));
-    TR_HIP(linear_wgrad(c, w.GQKV, 3 * D, X, D, R, 3 * D, D, P.gr(sp + ".Wqkv.weight"), P.gr(sp + ".Wqkv.bias")));
+    LG_HIP(rotary_split_bwd(w.GQ, w.GK, w.GV, sb.Q, sb.K, s.COS, s.SIN, R, H, w.GQKV, w.GCOS, w.GSIN, c.st));
+    LG_HIP(linear_wgrad(c, w.GQKV, 3 * D, X, D, R, 3 * D, D, P.gr(sp + ".Wqkv.weight"), P.gr(sp + ".Wqkv.bias")));
     // transformers.<l>.* are final: a data-parallel caller starts this bucket's all-reduce now,
     // under the remaining layers' backward (DDP's overlap, train.py:309)
     handle_grad_ready(h, l, stream);
-    TR_HIP(linear_dgrad(c, w.GQKV, 3 * D, R, 3 * D, P.w(sp + ".Wqkv.weight"), D, w.GX, D, 1.f));
+    LG_HIP(linear_dgrad(c, w.GQKV, 3 * D, R, 3 * D, P.w(sp + ".Wqkv.weight"), D, w.GX, D, 1.f));
   }
   // GX = d/d(X0): input_proj (:486-487) and the input descriptors
   if (d.proj) {
-    TR_HIP(linear_wgrad(c, w.GX, D, s.Din, d.din, R, D, d.din, P.gr("input_proj.weight"), P.gr("input_proj.bias")));
-    if (grad_desc0) TR_HIP(linear_dgrad(c, w.GX, D, R0, D, P.w("input_proj.weight"), d.din, grad_desc0, d.din));
-    if (grad_desc1) TR_HIP(linear_dgrad(c, w.GX + o1, D, R - R0, D, P.w("input_proj.weight"), d.din, grad_desc1, d.din));
+    LG_HIP(linear_wgrad(c, w.GX, D, s.Din, d.din, R, D, d.din, P.gr("input_proj.weight"), P.gr("input_proj.bias")));
+    if (grad_desc0) LG_HIP(linear_dgrad(c, w.GX, D, R0, D, P.w("input_proj.weight"), d.din, grad_desc0, d.din));
+    if (grad_desc1) LG_HIP(linear_dgrad(c, w.GX + o1, D, R - R0, D, P.w("input_proj.weight"), d.din, grad_desc1, d.din));
   } else {
-    if (grad_desc0) TR_HIP(hipMemcpyAsync(grad_desc0, w.GX, o1 * 4, hipMemcpyDeviceToDevice, c.st));
-    if (grad_desc1) TR_HIP(hipMemcpyAsync(grad_desc1, w.GX + o1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+    if (grad_desc0) LG_HIP(hipMemcpyAsync(grad_desc0, w.GX, o1 * 4, hipMemcpyDeviceToDevice, c.st));
+    if (grad_desc1) LG_HIP(hipMemcpyAsync(grad_desc1, w.GX + o1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   }
   // posenc (:63-77): d/d(Wr, condition_modulation) from the rotary's cos / sin gradients
   float* gWr = P.gr("posenc.Wr.weight");
@@ -536,7 +528,7 @@ int lg_train_backward(lg_handle_t* h, const float* const* params, const lg_input
   float* gbc = P.gr("posenc.condition_modulation.bias");
   // any requested subset (a frozen parameter's gradient pointer is null)
   if (gWr || gWc || gbc)
-    TR_HIP(pe_backward(s.PEX, s.COS, s.SIN, w.GCOS, w.GSIN, R, R0, (float)M, (float)N, d.m_in, w.PART, gWr, gWc, gbc, c.st));
+    LG_HIP(pe_backward(s.PEX, s.COS, s.SIN, w.GCOS, w.GSIN, R, R0, (float)M, (float)N, d.m_in, w.PART, gWr, gWc, gbc, c.st));
   handle_grad_ready(h, -1, stream);  // input_proj.*, posenc.*
   return LG_OK;
 }
@@ -611,7 +603,7 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
     return fail(LG_E_INVALID, "token_confidence exists for layers 0..n_layers-2 only (lightglue.py:395-397)");
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
-  TR_HIP(hipSetDevice(handle_device(h)));
+  LG_HIP(hipSetDevice(handle_device(h)));
   const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, grads};
   const std::string a = "log_assignment." + std::to_string(layer);
@@ -619,60 +611,60 @@ int head_backward(lg_handle_t* h, const float* const* params, int32_t layer, con
   const size_t o1 = (size_t)R0 * D;
   const float* Wf = P.w(a + ".final_proj.weight");
   const float* wm = P.w(a + ".matchability.weight");
-  TR_HIP(hipMemcpyAsync(s.X, desc0, o1 * 4, hipMemcpyDeviceToDevice, c.st));
-  TR_HIP(hipMemcpyAsync(s.X + o1, desc1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+  LG_HIP(hipMemcpyAsync(s.X, desc0, o1 * 4, hipMemcpyDeviceToDevice, c.st));
+  LG_HIP(hipMemcpyAsync(s.X + o1, desc1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   if (!from_forward) {
     // recompute: md = final_proj(desc) / 4, z = matchability(desc), sim = md0 md1^T (:306-315)
-    TR_HIP(linear(c, s.X, D, R, D, Wf, P.w(a + ".final_proj.bias"), D, s.MD, D, 0.f, 0.25f));
-    TR_HIP(gemv256(s.X, R, wm, P.w(a + ".matchability.bias"), s.Z, c.st));
+    LG_HIP(linear(c, s.X, D, R, D, Wf, P.w(a + ".final_proj.bias"), D, s.MD, D, 0.f, 0.25f));
+    LG_HIP(gemv256(s.X, R, wm, P.w(a + ".matchability.bias"), s.Z, c.st));
     TGemm g{s.MD, s.MD + o1, s.SIM, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
-    TR_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
+    LG_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
+    LG_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
   }
   // sigmoid_log_double_softmax backward (:284-296)
   if (gt) {
-    TR_HIP(la_grad_gt(s.SIM, gt->gta, gt->gt0, gt->gt1, s_in, s_dust, s.LSER, s.LSEC, B, M, N, s.RS, s.RS + R0, s.GD,
+    LG_HIP(la_grad_gt(s.SIM, gt->gta, gt->gt0, gt->gt1, s_in, s_dust, s.LSER, s.LSEC, B, M, N, s.RS, s.RS + R0, s.GD,
                       s.GD + R0, c.part, c.st));
   } else {
-    TR_HIP(la_grad_sums(la_grad, s_in, s_dust, B, M, N, s.RS, s.RS + R0, s.GD, s.GD + R0, c.part, c.st));
-    TR_HIP(la_grad_sim(s.SIM, la_grad, s_in, s.LSER, s.LSEC, s.RS, s.RS + R0, grad_similarity, B, M, N, c.st));
+    LG_HIP(la_grad_sums(la_grad, s_in, s_dust, B, M, N, s.RS, s.RS + R0, s.GD, s.GD + R0, c.part, c.st));
+    LG_HIP(la_grad_sim(s.SIM, la_grad, s_in, s.LSER, s.LSEC, s.RS, s.RS + R0, grad_similarity, B, M, N, c.st));
   }
-  TR_HIP(la_grad_z(s.Z, s.RS, s.GD, R, s.GZ, c.st));
+  LG_HIP(la_grad_z(s.Z, s.RS, s.GD, R, s.GZ, c.st));
   // d/d(final_proj output) = d/d(md) / 4: gmd0 = gsim md1, gmd1 = gsim^T md0
   if (N % 16 == 0) {  // gmd0 on the bf16x6 GEMM through md1^T; the f32 MFMA kernel on md1 as is otherwise
     float* md1t = s.GMD + o1;  // [B][D][N]: free until the d(md1) product below
-    TR_HIP(transpose_batched(s.MD + o1, N, D, B, md1t, c.st));
+    LG_HIP(transpose_batched(s.MD + o1, N, D, B, md1t, c.st));
     TGemm g{s.SIM, md1t, s.GMD, N, N, D, (long long)M * N, (long long)D * N, (long long)M * D, M, D, N, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   } else {
     TGemm g{s.SIM, s.MD + o1, s.GMD, N, D, D, (long long)M * N, (long long)N * D, (long long)M * D, M, D, N, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st));
   }
   {
     TGemm g{s.SIM, s.MD, s.GMD + o1, N, D, D, (long long)M * N, (long long)M * D, (long long)N * D, N, D, M, B, 0.25f, 0.f, nullptr};
-    TR_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
   }
-  TR_HIP(linear_wgrad(c, s.GMD, D, s.X, D, R, D, D, P.gr(a + ".final_proj.weight"), P.gr(a + ".final_proj.bias")));
+  LG_HIP(linear_wgrad(c, s.GMD, D, s.X, D, R, D, D, P.gr(a + ".final_proj.weight"), P.gr(a + ".final_proj.bias")));
   const bool tok = grad_token0 || grad_token1;
   if (tok) {  // TokenConfidence's logit gradient (:108-122), [R]
-    if (grad_token0) TR_HIP(hipMemcpyAsync(s.GT, grad_token0, (size_t)R0 * 4, hipMemcpyDeviceToDevice, c.st));
-    else TR_HIP(hipMemsetAsync(s.GT, 0, (size_t)R0 * 4, c.st));
-    if (grad_token1) TR_HIP(hipMemcpyAsync(s.GT + R0, grad_token1, (size_t)(R - R0) * 4, hipMemcpyDeviceToDevice, c.st));
-    else TR_HIP(hipMemsetAsync(s.GT + R0, 0, (size_t)(R - R0) * 4, c.st));
+    if (grad_token0) LG_HIP(hipMemcpyAsync(s.GT, grad_token0, (size_t)R0 * 4, hipMemcpyDeviceToDevice, c.st));
+    else LG_HIP(hipMemsetAsync(s.GT, 0, (size_t)R0 * 4, c.st));
+    if (grad_token1) LG_HIP(hipMemcpyAsync(s.GT + R0, grad_token1, (size_t)(R - R0) * 4, hipMemcpyDeviceToDevice, c.st));
+    else LG_HIP(hipMemsetAsync(s.GT + R0, 0, (size_t)(R - R0) * 4, c.st));
   }
   const std::string t = "token_confidence." + std::to_string(layer) + ".token.0";
   // matchability's and the token linear's gradients in one read of X (TokenConfidence, :108-122:
   // logits = token(desc.detach()) -> the token Linear only)
-  TR_HIP(head_vec_grads(s.X, R, s.GZ, tok ? s.GT : nullptr, c.part, P.gr(a + ".matchability.weight"),
+  LG_HIP(head_vec_grads(s.X, R, s.GZ, tok ? s.GT : nullptr, c.part, P.gr(a + ".matchability.weight"),
                         P.gr(a + ".matchability.bias"), tok ? P.gr(t + ".weight") : nullptr,
                         tok ? P.gr(t + ".bias") : nullptr, c.st));
   if (grad_desc0) {
-    TR_HIP(linear_dgrad(c, s.GMD, D, R0, D, Wf, D, grad_desc0, D));
-    TR_HIP(rank1_add256(grad_desc0, R0, s.GZ, wm, c.st));
+    LG_HIP(linear_dgrad(c, s.GMD, D, R0, D, Wf, D, grad_desc0, D));
+    LG_HIP(rank1_add256(grad_desc0, R0, s.GZ, wm, c.st));
   }
   if (grad_desc1) {
-    TR_HIP(linear_dgrad(c, s.GMD + o1, D, R - R0, D, Wf, D, grad_desc1, D));
-    TR_HIP(rank1_add256(grad_desc1, R - R0, s.GZ + R0, wm, c.st));
+    LG_HIP(linear_dgrad(c, s.GMD + o1, D, R - R0, D, Wf, D, grad_desc1, D));
+    LG_HIP(rank1_add256(grad_desc1, R - R0, s.GZ + R0, wm, c.st));
   }
   return LG_OK;
 }
@@ -729,7 +721,7 @@ int lg_head_nll_forward(lg_handle_t* h, const float* const* params, int32_t laye
     return fail(LG_E_INVALID, "token_confidence exists for layers 0..n_layers-2 only (lightglue.py:395-397)");
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
-  TR_HIP(hipSetDevice(handle_device(h)));
+  LG_HIP(hipSetDevice(handle_device(h)));
   const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, nullptr};
   const std::string a = "log_assignment." + std::to_string(layer);
@@ -739,21 +731,21 @@ int lg_head_nll_forward(lg_handle_t* h, const float* const* params, int32_t laye
     const float* dsc = im ? desc1 : desc0;
     const int rows = im ? R - R0 : R0;
     const size_t o = im ? o1 : 0;
-    TR_HIP(linear(c, dsc, D, rows, D, P.w(a + ".final_proj.weight"), P.w(a + ".final_proj.bias"), D, s.MD + o, D, 0.f,
+    LG_HIP(linear(c, dsc, D, rows, D, P.w(a + ".final_proj.weight"), P.w(a + ".final_proj.bias"), D, s.MD + o, D, 0.f,
                   0.25f));
-    TR_HIP(gemv256(dsc, rows, P.w(a + ".matchability.weight"), P.w(a + ".matchability.bias"), s.Z + (im ? R0 : 0), c.st));
+    LG_HIP(gemv256(dsc, rows, P.w(a + ".matchability.weight"), P.w(a + ".matchability.bias"), s.Z + (im ? R0 : 0), c.st));
   }
   {
     TGemm g{s.MD, s.MD + o1, s.SIM, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   }
-  TR_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
-  TR_HIP(la_nll(s.SIM, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, gt_assignment, gt_matches0, gt_matches1, mode, balancing, out,
+  LG_HIP(sim_lse(s.SIM, B, M, N, s.LSER, s.LSEC, c.part, c.st));
+  LG_HIP(la_nll(s.SIM, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, gt_assignment, gt_matches0, gt_matches1, mode, balancing, out,
                 argmax0, argmax1, s.NLLP, c.st));
   if (token_logits0 || token_logits1) {
     const std::string t = "token_confidence." + std::to_string(layer) + ".token.0";
-    if (token_logits0) TR_HIP(gemv256(desc0, R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits0, c.st));
-    if (token_logits1) TR_HIP(gemv256(desc1, R - R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits1, c.st));
+    if (token_logits0) LG_HIP(gemv256(desc0, R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits0, c.st));
+    if (token_logits1) LG_HIP(gemv256(desc1, R - R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits1, c.st));
   }
   return LG_OK;
 }
@@ -770,7 +762,7 @@ int lg_head_forward(lg_handle_t* h, const float* const* params, int32_t layer, c
     return fail(LG_E_INVALID, "token_confidence exists for layers 0..n_layers-2 only (lightglue.py:395-397)");
   HeadScratch s = carve_head_scratch((char*)scratch, B, M, N);
   if (scratch_bytes < s.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(s.bytes));
-  TR_HIP(hipSetDevice(handle_device(h)));
+  LG_HIP(hipSetDevice(handle_device(h)));
   const Ctx c{(hipStream_t)stream, s.WS, s.ws_floats, s.PART};
   const Params P{h, params, nullptr};
   const std::string a = "log_assignment." + std::to_string(layer);
@@ -783,20 +775,20 @@ int lg_head_forward(lg_handle_t* h, const float* const* params, int32_t layer, c
     const float* dsc = im ? desc1 : desc0;
     const int rows = im ? R - R0 : R0;
     const size_t o = im ? o1 : 0;
-    TR_HIP(linear(c, dsc, D, rows, D, P.w(a + ".final_proj.weight"), P.w(a + ".final_proj.bias"), D, s.MD + o, D, 0.f,
+    LG_HIP(linear(c, dsc, D, rows, D, P.w(a + ".final_proj.weight"), P.w(a + ".final_proj.bias"), D, s.MD + o, D, 0.f,
                   0.25f));
-    TR_HIP(gemv256(dsc, rows, P.w(a + ".matchability.weight"), P.w(a + ".matchability.bias"), s.Z + (im ? R0 : 0), c.st));
+    LG_HIP(gemv256(dsc, rows, P.w(a + ".matchability.weight"), P.w(a + ".matchability.bias"), s.Z + (im ? R0 : 0), c.st));
   }
   {
     TGemm g{s.MD, s.MD + o1, sim, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B, 1.f, 0.f, nullptr};
-    TR_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
   }
-  TR_HIP(sim_lse(sim, B, M, N, s.LSER, s.LSEC, c.part, c.st));
-  TR_HIP(la_forward(sim, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, log_assignment, c.st));
+  LG_HIP(sim_lse(sim, B, M, N, s.LSER, s.LSEC, c.part, c.st));
+  LG_HIP(la_forward(sim, s.LSER, s.LSEC, s.Z, s.Z + R0, B, M, N, log_assignment, c.st));
   if (token_logits0 || token_logits1) {  // TokenConfidence's Linear (:109-110)
     const std::string t = "token_confidence." + std::to_string(layer) + ".token.0";
-    if (token_logits0) TR_HIP(gemv256(desc0, R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits0, c.st));
-    if (token_logits1) TR_HIP(gemv256(desc1, R - R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits1, c.st));
+    if (token_logits0) LG_HIP(gemv256(desc0, R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits0, c.st));
+    if (token_logits1) LG_HIP(gemv256(desc1, R - R0, P.w(t + ".weight"), P.w(t + ".bias"), token_logits1, c.st));
   }
   return LG_OK;
 }
@@ -814,8 +806,8 @@ int lg_train_gemm(const float* A, const float* Bm, float* C, int64_t lda, int64_
                   const float* bias, int32_t ta, int32_t tb, void* workspace, size_t workspace_bytes, void* stream) {
   if (!A || !Bm || !C || M < 0 || N < 0 || K < 0 || batch < 0) return fail(LG_E_INVALID, "bad argument");
   TGemm g{A, Bm, C, lda, ldb, ldc, sA, sB, sC, M, N, K, batch, alpha, beta, bias};
-  TR_HIP(tgemm(g, ta != 0, tb != 0, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream));
-  TR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  LG_HIP(tgemm(g, ta != 0, tb != 0, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream));
+  LG_HIP(hipStreamSynchronize((hipStream_t)stream));
   return LG_OK;
 }
 
@@ -837,8 +829,8 @@ int lg_train_gemm_ex(const float* A, const float* Bm, float* C, int64_t lda, int
   g.colsumA = colsumA;
   const hipError_t e = tgemm(g, ta != 0, tb != 0, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(LG_E_INVALID, "no route of the training GEMM takes these operands");
-  TR_HIP(e);
-  TR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  LG_HIP(e);
+  LG_HIP(hipStreamSynchronize((hipStream_t)stream));
   return LG_OK;
 }
 
@@ -846,8 +838,8 @@ int lg_train_attention(const float* q, const float* k, const float* v, int32_t B
                        float scale, float* o, float* lse, void* stream) {
   if (!q || !k || !v || !o || !lse || B < 0 || H <= 0 || H * 64 != D || Nq < 0 || Nk <= 0)
     return fail(LG_E_INVALID, "bad argument");
-  TR_HIP(tattn_forward(attn_args(q, k, v, o, lse, B, H, Nq, Nk, scale), (hipStream_t)stream));
-  TR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  LG_HIP(tattn_forward(attn_args(q, k, v, o, lse, B, H, Nq, Nk, scale), (hipStream_t)stream));
+  LG_HIP(hipStreamSynchronize((hipStream_t)stream));
   return LG_OK;
 }
 
@@ -858,16 +850,16 @@ int lg_train_attention_backward(const float* q, const float* k, const float* v, 
       H * 64 != D || Nq < 0 || Nk <= 0)
     return fail(LG_E_INVALID, "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  TR_HIP(attn_delta(o, grad_o, D, B, H, Nq, delta_ws, st));
-  TR_HIP(hipMemsetAsync(grad_q, 0, (size_t)B * Nq * D * 4, st));
+  LG_HIP(attn_delta(o, grad_o, D, B, H, Nq, delta_ws, st));
+  LG_HIP(hipMemsetAsync(grad_q, 0, (size_t)B * Nq * D * 4, st));
   TAttn a = attn_args(q, k, v, (float*)o, (float*)lse, B, H, Nq, Nk, scale);
   a.dO = grad_o;
   a.delta = delta_ws;
   a.dQ = grad_q;
   a.dK = grad_k;
   a.dV = grad_v;
-  TR_HIP(tattn_backward(a, st));
-  TR_HIP(hipStreamSynchronize(st));
+  LG_HIP(tattn_backward(a, st));
+  LG_HIP(hipStreamSynchronize(st));
   return LG_OK;
 }
 

@@ -9,24 +9,13 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
 #include "common.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
 using namespace lg;
-
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define LIN_HIP(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int kSlots = 8;  // 0/1: max|A0|, max|A1|; 2/3: their images; 4: output; 5: values; 6: max|res|
 enum { S_IN0 = 0, S_IN1 = 1, S_A0 = 2, S_A1 = 3, S_OUT = 4, S_OUTV = 5, S_RES = 6 };
@@ -178,24 +167,24 @@ int run_x6(const lg_linear_args_t& a, const Layout& L, char* ws, const RowMask& 
       float* c1 = reinterpret_cast<float*>(ws + L.cos1);
       const size_t n = (size_t)R * 32;
       hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c1, 1.f, n);
-      LIN_HIP(hipGetLastError());
-      LIN_HIP(hipMemsetAsync(ws + L.sin0, 0, n * 4, st));
+      LG_HIP(hipGetLastError());
+      LG_HIP(hipMemsetAsync(ws + L.sin0, 0, n * 4, st));
       hl.cosb = c1;
       hl.sinb = reinterpret_cast<float*>(ws + L.sin0);
     }
     g.out_scale = 1.f;
     g.hl = hl;
-    LIN_HIP(gemm_x6(g, a.epi == LG_LIN_QKV_ROT ? EPI_QKV_ROT : EPI_CROSS_QKV, 1, st));
+    LG_HIP(gemm_x6(g, a.epi == LG_LIN_QKV_ROT ? EPI_QKV_ROT : EPI_CROSS_QKV, 1, st));
     return LG_OK;
   }
   if (a.epi == LG_LIN_LN_GELU) {
     float* h1 = reinterpret_cast<float*>(ws + L.h1);
-    LIN_HIP(hipMemsetAsync(h1, 0, (size_t)R * 512 * 4, st));
+    LG_HIP(hipMemsetAsync(h1, 0, (size_t)R * 512 * 4, st));
     g.out_scale = 1.f; g.Y = h1; g.ldy = 512;
-    LIN_HIP(gemm_x6(g, EPI_STORE, 1, st));
-    LIN_HIP(layernorm_gelu_512(h1, a.ln_g, a.ln_b, R, nullptr, 0, range_none(), st));
+    LG_HIP(gemm_x6(g, EPI_STORE, 1, st));
+    LG_HIP(layernorm_gelu_512(h1, a.ln_g, a.ln_b, R, nullptr, 0, range_none(), st));
     // the row kernel does not look at the mask: dead rows come back as LN + GELU of a zero row
-    LIN_HIP(hipMemcpyAsync(a.yp_rows, h1, (size_t)R * 512 * 4, hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(a.yp_rows, h1, (size_t)R * 512 * 4, hipMemcpyDeviceToDevice, st));
     return LG_OK;
   }
   // LG_LIN_STORE: one pass per fp32 destination (the rows, and the "planes" stand-in yp_rows)
@@ -211,32 +200,32 @@ int run_x6(const lg_linear_args_t& a, const Layout& L, char* ws, const RowMask& 
     if (a.res2) {  // res | res2 as one array
       float* rt = reinterpret_cast<float*>(ws + L.rtmp);
       if (a.res2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(rt, rowb, a.res, (size_t)a.ldr * 4, rowb, a.res2_row0, hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(rt, rowb, a.res, (size_t)a.ldr * 4, rowb, a.res2_row0, hipMemcpyDeviceToDevice, st));
       if (R - a.res2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(rt + (size_t)a.res2_row0 * Nout, rowb, a.res2, (size_t)a.ldr * 4, rowb, R - a.res2_row0,
-                                 hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(rt + (size_t)a.res2_row0 * Nout, rowb, a.res2, (size_t)a.ldr * 4, rowb, R - a.res2_row0,
+                                hipMemcpyDeviceToDevice, st));
       p.res = rt; p.ldr = Nout;
     }
     if (Y2) {  // Y | Y2 as one array, starting from the caller's contents (dead rows keep them)
       if (a.y2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(ytmp, rowb, Y, (size_t)ldy * 4, rowb, a.y2_row0, hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(ytmp, rowb, Y, (size_t)ldy * 4, rowb, a.y2_row0, hipMemcpyDeviceToDevice, st));
       if (R - a.y2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(ytmp + (size_t)a.y2_row0 * Nout, rowb, Y2, (size_t)ldy * 4, rowb, R - a.y2_row0,
-                                 hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(ytmp + (size_t)a.y2_row0 * Nout, rowb, Y2, (size_t)ldy * 4, rowb, R - a.y2_row0,
+                                hipMemcpyDeviceToDevice, st));
       p.Y = ytmp; p.ldy = Nout;
     }
-    LIN_HIP(gemm_x6(p, EPI_STORE, 1, st));
+    LG_HIP(gemm_x6(p, EPI_STORE, 1, st));
     if (a.relu) {
       const size_t n = (size_t)R * Nout;
       hipLaunchKernelGGL(relu_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p.Y, p.ldy, R, Nout, rm);
-      LIN_HIP(hipGetLastError());
+      LG_HIP(hipGetLastError());
     }
     if (Y2) {
       if (a.y2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(Y, (size_t)ldy * 4, ytmp, rowb, rowb, a.y2_row0, hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(Y, (size_t)ldy * 4, ytmp, rowb, rowb, a.y2_row0, hipMemcpyDeviceToDevice, st));
       if (R - a.y2_row0 > 0)
-        LIN_HIP(hipMemcpy2DAsync(Y2, (size_t)ldy * 4, ytmp + (size_t)a.y2_row0 * Nout, rowb, rowb, R - a.y2_row0,
-                                 hipMemcpyDeviceToDevice, st));
+        LG_HIP(hipMemcpy2DAsync(Y2, (size_t)ldy * 4, ytmp + (size_t)a.y2_row0 * Nout, rowb, rowb, R - a.y2_row0,
+                                hipMemcpyDeviceToDevice, st));
     }
   }
   return LG_OK;
@@ -272,7 +261,7 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
   if (a.precision == LG_PREC_X6) {
     const int rc = run_x6(a, L, ws, rm, st);
     if (rc != LG_OK) return rc;
-    LIN_HIP(hipStreamSynchronize(st));
+    LG_HIP(hipStreamSynchronize(st));
     return LG_OK;
   }
 
@@ -284,20 +273,20 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
   const bool qkv = a.epi == LG_LIN_QKV_ROT || a.epi == LG_LIN_CROSS_QKV;
 
   // ---- range table, A plane images (each half its own exponent)
-  LIN_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
-  LIN_HIP(hipMemsetAsync(a0p, 0, (size_t)2 * RP * K0 * 2, st));
-  if (K1) LIN_HIP(hipMemsetAsync(a1p, 0, (size_t)2 * RP * K1 * 2, st));
+  LG_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
+  LG_HIP(hipMemsetAsync(a0p, 0, (size_t)2 * RP * K0 * 2, st));
+  if (K1) LG_HIP(hipMemsetAsync(a1p, 0, (size_t)2 * RP * K1 * 2, st));
   auto absmax_half = [&](const float* x, int k, int ld, int slot) {
     if (ld == k && !rm.cnt) return range_absmax(x, (size_t)R * k, rtab, slot, st);
     return range_absmax_rows(x, R, k, ld, 0, rm, rtab, slot, st);  // live rows only, as a ragged batch
   };
-  LIN_HIP(absmax_half(a.A0, K0, a.lda0, S_IN0));
-  if (K1) LIN_HIP(absmax_half(a.A1, K1, a.lda1, S_IN1));
-  LIN_HIP(rows_to_planes(a.A0, R, K0, a.lda0, a0p, RP, 0, RangeOut{rtab, S_IN0, -1, 1.f, 0.f, 0.f, S_A0, kRangeTrack}, st,
-                         nullptr, &rm));
+  LG_HIP(absmax_half(a.A0, K0, a.lda0, S_IN0));
+  if (K1) LG_HIP(absmax_half(a.A1, K1, a.lda1, S_IN1));
+  LG_HIP(rows_to_planes(a.A0, R, K0, a.lda0, a0p, RP, 0, RangeOut{rtab, S_IN0, -1, 1.f, 0.f, 0.f, S_A0, kRangeTrack}, st,
+                        nullptr, &rm));
   if (K1)
-    LIN_HIP(rows_to_planes(a.A1, R, K1, a.lda1, a1p, RP, 0, RangeOut{rtab, S_IN1, -1, 1.f, 0.f, 0.f, S_A1, kRangeTrack}, st,
-                           nullptr, &rm));
+    LG_HIP(rows_to_planes(a.A1, R, K1, a.lda1, a1p, RP, 0, RangeOut{rtab, S_IN1, -1, 1.f, 0.f, 0.f, S_A1, kRangeTrack}, st,
+                          nullptr, &rm));
   if (a.poison) {
     const size_t n0 = (size_t)RP * K0, n1 = (size_t)RP * K1;
     hipLaunchKernelGGL(poison_rows_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, a0p, (long long)RP * K0, RP,
@@ -305,38 +294,38 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
     if (K1)
       hipLaunchKernelGGL(poison_rows_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, a1p, (long long)RP * K1,
                          RP, K1, R, rm);
-    LIN_HIP(hipGetLastError());
+    LG_HIP(hipGetLastError());
   }
 
   // ---- weight planes and range statistics as at load time (one read-back)
   // stats: [0] max|W|; [2,3] L1 / bias max of the whole matrix or the key rows; [4,5] value rows; [6] LN bound
-  LIN_HIP(hipMemsetAsync(stats, 0, 16 * sizeof(float), st));
-  LIN_HIP(absmax(a.W, (size_t)Nout * K, stats, st));
+  LG_HIP(hipMemsetAsync(stats, 0, 16 * sizeof(float), st));
+  LG_HIP(absmax(a.W, (size_t)Nout * K, stats, st));
   if (qkv) {
     const size_t k0 = a.epi == LG_LIN_QKV_ROT ? 256 : 0, v0 = k0 + 256;
-    LIN_HIP(weight_range_stats(a.W + k0 * K, 256, K, a.bias + k0, stats + 2, st));
-    LIN_HIP(weight_range_stats(a.W + v0 * K, 256, K, a.bias + v0, stats + 4, st));
+    LG_HIP(weight_range_stats(a.W + k0 * K, 256, K, a.bias + k0, stats + 2, st));
+    LG_HIP(weight_range_stats(a.W + v0 * K, 256, K, a.bias + v0, stats + 4, st));
   } else {
-    LIN_HIP(weight_range_stats(a.W, Nout, K, a.bias, stats + 2, st));
+    LG_HIP(weight_range_stats(a.W, Nout, K, a.bias, stats + 2, st));
   }
-  if (a.epi == LG_LIN_LN_GELU) LIN_HIP(layernorm_bound(a.ln_g, a.ln_b, 512, stats + 6, st));
+  if (a.epi == LG_LIN_LN_GELU) LG_HIP(layernorm_bound(a.ln_g, a.ln_b, 512, stats + 6, st));
   if (a.res) {
     const int r0 = a.res2 ? a.res2_row0 : R;
-    LIN_HIP(range_absmax_rows(a.res, r0, Nout, a.ldr, 0, RowMask{}, rtab, S_RES, st));
-    if (a.res2) LIN_HIP(range_absmax_rows(a.res2, R - r0, Nout, a.ldr, 0, RowMask{}, rtab, S_RES, st));
+    LG_HIP(range_absmax_rows(a.res, r0, Nout, a.ldr, 0, RowMask{}, rtab, S_RES, st));
+    if (a.res2) LG_HIP(range_absmax_rows(a.res2, R - r0, Nout, a.ldr, 0, RowMask{}, rtab, S_RES, st));
   }
   float hs[16];
   unsigned htab[kSlots * kRangeStride];
-  LIN_HIP(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, st));
-  LIN_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
-  LIN_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
   int sw = 0;
   if (hs[0] > 0.f && std::isfinite(hs[0])) {
     int E;
     (void)std::frexp(hs[0], &E);  // max = m 2^E, m in [0.5, 1)
     sw = std::min(std::max(4 - E, -100), 100);
   }
-  LIN_HIP(split_weight_h3(a.W, Nout, K, std::ldexp(1.f, sw), wp, st));
+  LG_HIP(split_weight_h3(a.W, Nout, K, std::ldexp(1.f, sw), wp, st));
 
   GemmH3Args g;
   memset(&g, 0, sizeof(g));
@@ -366,19 +355,19 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
       g.ro = RangeOut{rtab, S_A0, in1, hs[2] * os, hs[2] * os, hs[3] * os + (a.res ? tab_max(htab, S_RES) : 0.f), S_OUT,
                       kRangeTrack};
     }
-    LIN_HIP(gemm_h3(g, EPI_STORE, st));
+    LG_HIP(gemm_h3(g, EPI_STORE, st));
   } else if (a.epi == LG_LIN_LN_GELU) {
     const RangeOut ro_h{rtab, -1, -1, 0.f, 0.f, hs[6], S_OUT, kRangeTrack};
     a.bound_out = hs[6];
     if (a.ln_route == 1) {
       float* h1 = reinterpret_cast<float*>(ws + L.h1);
-      LIN_HIP(hipMemsetAsync(h1, 0, (size_t)R * 512 * 4, st));
+      LG_HIP(hipMemsetAsync(h1, 0, (size_t)R * 512 * 4, st));
       g.Y = h1; g.ldy = 512;
-      LIN_HIP(gemm_h3(g, EPI_STORE, st));
-      LIN_HIP(layernorm_gelu_512(h1, a.ln_g, a.ln_b, R, yp, RP, ro_h, st));
+      LG_HIP(gemm_h3(g, EPI_STORE, st));
+      LG_HIP(layernorm_gelu_512(h1, a.ln_g, a.ln_b, R, yp, RP, ro_h, st));
     } else {
       g.Yp = yp; g.yps = yps; g.yrows_pad = RP; g.ln_g = a.ln_g; g.ln_b = a.ln_b; g.ro = ro_h;
-      LIN_HIP(gemm_h3(g, EPI_LN_GELU, st));
+      LG_HIP(gemm_h3(g, EPI_LN_GELU, st));
     }
   } else {
     HeadLayout hl;
@@ -389,12 +378,12 @@ int lg_linear(lg_linear_args_t* args, void* workspace, size_t workspace_bytes, v
     const float kf = a.epi == LG_LIN_QKV_ROT ? 1.5f : std::fabs(a.qk_scale);
     g.ro = RangeOut{rtab, S_A0, -1, hs[2] * kf, 0.f, hs[3] * kf, S_OUT, kRangeTrack};
     g.ro_v = RangeOut{rtab, S_A0, -1, hs[4], 0.f, hs[5], S_OUTV, kRangeTwoSided | kRangeTrack};
-    LIN_HIP(gemm_h3(g, a.epi == LG_LIN_QKV_ROT ? EPI_QKV_ROT : EPI_CROSS_QKV, st));
+    LG_HIP(gemm_h3(g, a.epi == LG_LIN_QKV_ROT ? EPI_QKV_ROT : EPI_CROSS_QKV, st));
   }
   if (!qkv && a.yp_rows && (a.want_planes || a.epi == LG_LIN_LN_GELU))
-    LIN_HIP(image_to_rows(yp, yps, RP, Nout, a.yp_rows, R, rtab, S_OUT, st));
-  LIN_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
-  LIN_HIP(hipStreamSynchronize(st));
+    LG_HIP(image_to_rows(yp, yps, RP, Nout, a.yp_rows, R, rtab, S_OUT, st));
+  LG_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
   a.exp_a0 = tab_exp(htab, S_A0);
   a.exp_a1 = K1 ? tab_exp(htab, S_A1) : a.exp_a0;
   a.exp_out = tab_exp(htab, S_OUT);
@@ -414,7 +403,7 @@ int lg_plane_roundtrip(const float* x, int32_t R, int32_t K, int32_t lshift, int
   const int RP = (R + 255) / 256 * 256;
   const size_t tabb = align256((size_t)2 * kRangeStride * sizeof(unsigned)), imgb = (size_t)2 * RP * K * 2;
   char* buf = nullptr;
-  LIN_HIP(hipMallocAsync((void**)&buf, tabb + imgb, st));
+  LG_HIP(hipMallocAsync((void**)&buf, tabb + imgb, st));
   unsigned* tab = reinterpret_cast<unsigned*>(buf);
   _Float16* img = reinterpret_cast<_Float16*>(buf + tabb);
   unsigned htab[2 * kRangeStride];

@@ -5,15 +5,10 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
 // flat-index limits of nn_match.hip: the dense outputs and the plane-image rows are indexed in int
 const char* shape_error(int64_t B, int64_t M, int64_t N, int64_t D) {
   if (B < 0 || M < 0 || N < 0 || D < 0) return "negative size";

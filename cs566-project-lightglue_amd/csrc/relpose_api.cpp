@@ -7,15 +7,8 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
-
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
-namespace {
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-}  // namespace
 
 extern "C" {
 

@@ -25,14 +25,14 @@
 
 #include "../../include/lightglue_mi355x.h"
 #include "../../include/superglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 #include "train.h"
 
 namespace lg {
-int api_fail(int code, const char* msg);
 const sg_config_t* sg_handle_config(const sg_handle* h);
 int sg_handle_device(const sg_handle* h);
-int sg_handle_weight_index(const sg_handle* h, const std::string& name);
+const WeightSchema& sg_handle_schema(const sg_handle* h);
 const BnSync* sg_handle_sync(const sg_handle* h);                 // sg_set_collective (null: one rank)
 void sg_handle_grad_ready(const sg_handle* h, int layer, void* stream);  // sg_set_grad_ready_hook
 }  // namespace lg
@@ -40,14 +40,6 @@ void sg_handle_grad_ready(const sg_handle* h, int layer, void* stream);  // sg_s
 namespace {
 
 using namespace lg;
-
-int fail(int code, const std::string& msg) { return api_fail(code, msg.c_str()); }
-
-#define ST_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int D = 256, H = 4;
 constexpr float kMomentum = 0.1f;  // nn.BatchNorm1d default
@@ -194,8 +186,8 @@ struct Params {
   const sg_handle_t* h;
   float* const* p;
   float* const* g;
-  float* w(const std::string& n) const { return p[sg_handle_weight_index(h, n)]; }
-  float* gr(const std::string& n) const { return g ? g[sg_handle_weight_index(h, n)] : nullptr; }
+  float* w(const std::string& n) const { return p[sg_handle_schema(h).find(n)]; }
+  float* gr(const std::string& n) const { return g ? g[sg_handle_schema(h).find(n)] : nullptr; }
 };
 
 struct Ctx {
@@ -329,7 +321,7 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
   if (d.cin == 3 && (!in->scores0 || !in->scores1)) return fail(LG_E_INVALID, "use_scores needs scores0/1");
   Saved s = carve_saved((char*)saved, d);
   if (saved_bytes < s.bytes) return fail(LG_E_WORKSPACE, "saved buffer too small: need " + std::to_string(s.bytes));
-  ST_HIP(hipSetDevice(sg_handle_device(h)));
+  LG_HIP(hipSetDevice(sg_handle_device(h)));
   // the forward's GEMMs run without split-k (no workspace)
   const Ctx c{(hipStream_t)stream, nullptr, 0, s.PART};
   const Params P{h, params, nullptr};
@@ -337,29 +329,29 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
   const size_t o1 = (size_t)R0;
   const int rows_of[2] = {R0, R - R0};
   // keypoint encoder (:89-104,274-275): [x, y(, score)] -> MLP with batch-statistics BatchNorm
-  ST_HIP(kenc_input(in->keypoints0, in->scores0, in->image_size0, (float)in->image_w0, (float)in->image_h0, B, M, d.cin,
+  LG_HIP(kenc_input(in->keypoints0, in->scores0, in->image_size0, (float)in->image_w0, (float)in->image_h0, B, M, d.cin,
                     s.KIN, c.st));
-  ST_HIP(kenc_input(in->keypoints1, in->scores1, in->image_size1, (float)in->image_w1, (float)in->image_h1, B, N, d.cin,
+  LG_HIP(kenc_input(in->keypoints1, in->scores1, in->image_size1, (float)in->image_w1, (float)in->image_h1, B, N, d.cin,
                     s.KIN + o1 * d.cin, c.st));
-  ST_HIP(hipMemcpyAsync(s.X0, in->descriptors0, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
-  ST_HIP(hipMemcpyAsync(s.X0 + o1 * D, in->descriptors1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+  LG_HIP(hipMemcpyAsync(s.X0, in->descriptors0, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
+  LG_HIP(hipMemcpyAsync(s.X0 + o1 * D, in->descriptors1, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   const int nk = (int)d.ch.size() - 1;
   const float* prev = s.KIN;
   for (int i = 1; i <= nk; ++i) {
     const std::string cv = conv_name("kenc.encoder", 3 * (i - 1));
     const int Ci = d.ch[i], Cp = d.ch[i - 1];
     if (i == nk) {  // desc + kenc(...) (:274-275)
-      ST_HIP(linear(c, prev, Cp, R, Cp, P.w(cv + ".weight"), P.w(cv + ".bias"), D, s.X0, D, 1.f));
+      LG_HIP(linear(c, prev, Cp, R, Cp, P.w(cv + ".weight"), P.w(cv + ".bias"), D, s.X0, D, 1.f));
       break;
     }
     const Enc& e = s.enc[i - 1];
-    ST_HIP(linear(c, prev, Cp, R, Cp, P.w(cv + ".weight"), P.w(cv + ".bias"), Ci, e.A, Ci));
+    LG_HIP(linear(c, prev, Cp, R, Cp, P.w(cv + ".weight"), P.w(cv + ".bias"), Ci, e.A, Ci));
     const std::string bn = conv_name("kenc.encoder", 3 * (i - 1) + 1);
     // both image sets; with a collective (data-parallel) their global batches' statistics
-    ST_HIP(bn_train_fwd_sets(e.A, Ci, rows_of, Ci, P.w(bn + ".weight"), P.w(bn + ".bias"), e.G, Ci, e.ST, c.part,
+    LG_HIP(bn_train_fwd_sets(e.A, Ci, rows_of, Ci, P.w(bn + ".weight"), P.w(bn + ".bias"), e.G, Ci, e.ST, c.part,
                              sg_handle_sync(h), c.st));
     for (int set = 0; set < 2; ++set)
-      ST_HIP(bn_running_update(P.w(bn + ".running_mean"), P.w(bn + ".running_var"), e.ST + set * 3 * Ci, Ci, kMomentum, c.st));
+      LG_HIP(bn_running_update(P.w(bn + ".running_mean"), P.w(bn + ".running_var"), e.ST + set * 3 * Ci, Ci, kMomentum, c.st));
     prev = e.G;
   }
   // AttentionalGNN (:142-170)
@@ -376,16 +368,16 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
         hg.add(P.w(pj + ".bias"), D, 1, false, false, y.BQKV + t * D);
       }
       hg.add(P.w(p + ".attn.merge.weight"), D, D, true, false, y.WM);
-      ST_HIP(head_gather_multi(hg, c.st));
+      LG_HIP(head_gather_multi(hg, c.st));
     }
     // q = proj0(x), k / v = proj1 / proj2(source) (:121-124): one GEMM over every row; the
     // attention pairs image-0 queries with image-0 (self) or image-1 (cross) keys and back
-    ST_HIP(linear(c, X, D, R, D, y.WQKV, y.BQKV, 3 * D, y.QKV, 3 * D));
+    LG_HIP(linear(c, X, D, R, D, y.WQKV, y.BQKV, 3 * D, y.QKV, 3 * D));
     const bool cross = d.type[l] == 1;
-    ST_HIP(tattn_forward(attn_args(y.QKV, 0, cross ? o1 : 0, y.O, y.LSE, B, M, cross ? N : M), c.st));
-    ST_HIP(tattn_forward(attn_args(y.QKV, o1, cross ? 0 : o1, y.O, y.LSE + lse1, B, N, cross ? M : N), c.st));
+    LG_HIP(tattn_forward(attn_args(y.QKV, 0, cross ? o1 : 0, y.O, y.LSE, B, M, cross ? N : M), c.st));
+    LG_HIP(tattn_forward(attn_args(y.QKV, o1, cross ? 0 : o1, y.O, y.LSE + lse1, B, N, cross ? M : N), c.st));
     // mlp(cat([x, merge(message)])) (:125-127,135-139) with batch-statistics BatchNorm per image set
-    ST_HIP(linear(c, y.O, D, R, D, y.WM, P.w(p + ".attn.merge.bias"), D, y.CAT + D, 2 * D));
+    LG_HIP(linear(c, y.O, D, R, D, y.WM, P.w(p + ".attn.merge.bias"), D, y.CAT + D, 2 * D));
     {  // mlp.0's input cat([x, message]) read from its two halves (x where it lies, the message in
        // CAT[:, 256:]) by the bf16x6 forward product and weight gradient: x is never copied into CAT[:, :256]
       TGemm g{X, P.w(p + ".mlp.0.weight"), y.H1, D, 2 * D, 2 * D, 0, 0, 0, R, 2 * D, 2 * D, 1, 1.f, 0.f,
@@ -393,32 +385,32 @@ int sg_train_forward(sg_handle_t* h, float* const* params, const sg_inputs_t* in
       g.A1 = y.CAT + D;
       g.lda1 = 2 * D;
       g.K0 = D;
-      ST_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
+      LG_HIP(tgemm(g, false, true, c.ws, c.ws_floats, c.st));
     }
-    ST_HIP(bn_train_fwd_sets(y.H1, 2 * D, rows_of, 2 * D, P.w(p + ".mlp.1.weight"), P.w(p + ".mlp.1.bias"), y.G, 2 * D,
+    LG_HIP(bn_train_fwd_sets(y.H1, 2 * D, rows_of, 2 * D, P.w(p + ".mlp.1.weight"), P.w(p + ".mlp.1.bias"), y.G, 2 * D,
                              y.ST, c.part, sg_handle_sync(h), c.st));
     for (int set = 0; set < 2; ++set)
-      ST_HIP(bn_running_update(P.w(p + ".mlp.1.running_mean"), P.w(p + ".mlp.1.running_var"), y.ST + set * 6 * D, 2 * D,
+      LG_HIP(bn_running_update(P.w(p + ".mlp.1.running_mean"), P.w(p + ".mlp.1.running_var"), y.ST + set * 6 * D, 2 * D,
                                kMomentum, c.st));
     // desc + delta (:166)
-    ST_HIP(linear_res(c, y.G, 2 * D, R, 2 * D, P.w(p + ".mlp.3.weight"), P.w(p + ".mlp.3.bias"), D, y.Y, D, X, D));
+    LG_HIP(linear_res(c, y.G, 2 * D, R, 2 * D, P.w(p + ".mlp.3.weight"), P.w(p + ".mlp.3.bias"), D, y.Y, D, X, D));
   }
   const float* XL = d.L ? s.lay[d.L - 1].Y : s.X0;
-  if (out->descriptors0) ST_HIP(hipMemcpyAsync(out->descriptors0, XL, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
+  if (out->descriptors0) LG_HIP(hipMemcpyAsync(out->descriptors0, XL, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
   if (out->descriptors1)
-    ST_HIP(hipMemcpyAsync(out->descriptors1, XL + o1 * D, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+    LG_HIP(hipMemcpyAsync(out->descriptors1, XL + o1 * D, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   // md = final_proj(desc); cost = md0^T md1 / sqrt(256) (:279-282)
-  ST_HIP(linear(c, XL, D, R, D, P.w("final_proj.weight"), P.w("final_proj.bias"), D, s.MD, D));
+  LG_HIP(linear(c, XL, D, R, D, P.w("final_proj.weight"), P.w("final_proj.bias"), D, s.MD, D));
   {
     TGemm g{s.MD, s.MD + o1 * D, s.COST, D, D, N, (long long)M * D, (long long)N * D, (long long)M * N, M, N, D, B,
             1.f / 16.f, 0.f, nullptr};
-    ST_HIP(tgemm(g, false, true, nullptr, 0, c.st));
+    LG_HIP(tgemm(g, false, true, nullptr, 0, c.st));
   }
   if (out->sinkhorn_cost)
-    ST_HIP(hipMemcpyAsync(out->sinkhorn_cost, s.COST, (size_t)B * M * N * 4, hipMemcpyDeviceToDevice, c.st));
-  ST_HIP(sk_train_forward(s.COST, P.w("bin_score"), B, M, N, d.T, s.CC, s.U, s.V, out->log_assignment, s.SKP, c.st));
+    LG_HIP(hipMemcpyAsync(out->sinkhorn_cost, s.COST, (size_t)B * M * N * 4, hipMemcpyDeviceToDevice, c.st));
+  LG_HIP(sk_train_forward(s.COST, P.w("bin_score"), B, M, N, d.T, s.CC, s.U, s.V, out->log_assignment, s.SKP, c.st));
   if (out->matches0 && out->matches1 && out->matching_scores0 && out->matching_scores1)
-    ST_HIP(filter_from_scores(out->log_assignment, B, M, N, sg_handle_config(h)->filter_threshold, s.FWS, out->matches0,
+    LG_HIP(filter_from_scores(out->log_assignment, B, M, N, sg_handle_config(h)->filter_threshold, s.FWS, out->matches0,
                               out->matches1, out->matching_scores0, out->matching_scores1, c.st));
   return LG_OK;
 }
@@ -433,7 +425,7 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
   if (saved_bytes < s.bytes) return fail(LG_E_WORKSPACE, "saved buffer too small");
   Scratch w = carve_scratch((char*)scratch, d);
   if (scratch_bytes < w.bytes) return fail(LG_E_WORKSPACE, "scratch too small: need " + std::to_string(w.bytes));
-  ST_HIP(hipSetDevice(sg_handle_device(h)));
+  LG_HIP(hipSetDevice(sg_handle_device(h)));
   const Ctx c{(hipStream_t)stream, w.WS, w.ws_floats, w.PART};
   const Params P{h, params, grads};
   const int B = d.B, M = d.M, N = d.N, R = d.R, R0 = d.R0;
@@ -441,28 +433,28 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
   const int rows_of[2] = {R0, R - R0};
   // Sinkhorn (:174-201) -> d/d cost, d/d bin_score
   if (grad_log_assignment) {
-    ST_HIP(sk_train_backward(s.CC, s.U, s.V, grad_log_assignment, grad_cost, B, M, N, d.T, w.GCOST, P.gr("bin_score"), w.SK,
+    LG_HIP(sk_train_backward(s.CC, s.U, s.V, grad_log_assignment, grad_cost, B, M, N, d.T, w.GCOST, P.gr("bin_score"), w.SK,
                              c.st));
   } else {
-    if (grad_cost) ST_HIP(hipMemcpyAsync(w.GCOST, grad_cost, (size_t)B * M * N * 4, hipMemcpyDeviceToDevice, c.st));
-    else ST_HIP(hipMemsetAsync(w.GCOST, 0, (size_t)B * M * N * 4, c.st));
-    if (float* g = P.gr("bin_score")) ST_HIP(hipMemsetAsync(g, 0, 4, c.st));
+    if (grad_cost) LG_HIP(hipMemcpyAsync(w.GCOST, grad_cost, (size_t)B * M * N * 4, hipMemcpyDeviceToDevice, c.st));
+    else LG_HIP(hipMemsetAsync(w.GCOST, 0, (size_t)B * M * N * 4, c.st));
+    if (float* g = P.gr("bin_score")) LG_HIP(hipMemsetAsync(g, 0, 4, c.st));
   }
   // cost = md0^T md1 / 16: gmd0 = gcost md1 / 16, gmd1 = gcost^T md0 / 16
   {
     TGemm g{w.GCOST, s.MD + o1 * D, w.GMD, N, D, D, (long long)M * N, (long long)N * D, (long long)M * D, M, D, N, B,
             1.f / 16.f, 0.f, nullptr};
-    ST_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, false, false, c.ws, c.ws_floats, c.st));
   }
   {
     TGemm g{w.GCOST, s.MD, w.GMD + o1 * D, N, D, D, (long long)M * N, (long long)M * D, (long long)N * D, N, D, M, B,
             1.f / 16.f, 0.f, nullptr};
-    ST_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
+    LG_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
   }
   const float* XL = d.L ? s.lay[d.L - 1].Y : s.X0;
-  ST_HIP(linear_wgrad(c, w.GMD, D, XL, D, R, D, D, P.gr("final_proj.weight"), P.gr("final_proj.bias")));
+  LG_HIP(linear_wgrad(c, w.GMD, D, XL, D, R, D, D, P.gr("final_proj.weight"), P.gr("final_proj.bias")));
   sg_handle_grad_ready(h, d.L, stream);  // final_proj.*, bin_score are final (DDP bucket overlap)
-  ST_HIP(linear_dgrad(c, w.GMD, D, R, D, P.w("final_proj.weight"), D, w.GX, D));
+  LG_HIP(linear_dgrad(c, w.GMD, D, R, D, P.w("final_proj.weight"), D, w.GX, D));
   const size_t lse1 = (size_t)B * H * M;
   float* GX = w.GX;
   float* GX2 = w.GX2;
@@ -471,14 +463,14 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
     const Lay& y = s.lay[l];
     const float* X = l == 0 ? s.X0 : s.lay[l - 1].Y;
     // delta = mlp.3(G): GX -> GG (d/d G)
-    ST_HIP(linear_wgrad(c, GX, D, y.G, 2 * D, R, D, 2 * D, P.gr(p + ".mlp.3.weight"), P.gr(p + ".mlp.3.bias")));
-    ST_HIP(linear_dgrad(c, GX, D, R, D, P.w(p + ".mlp.3.weight"), 2 * D, w.GG, 2 * D));
-    ST_HIP(bn_train_bwd_sets(y.H1, 2 * D, w.GG, 2 * D, rows_of, 2 * D, y.ST, P.w(p + ".mlp.1.weight"),
+    LG_HIP(linear_wgrad(c, GX, D, y.G, 2 * D, R, D, 2 * D, P.gr(p + ".mlp.3.weight"), P.gr(p + ".mlp.3.bias")));
+    LG_HIP(linear_dgrad(c, GX, D, R, D, P.w(p + ".mlp.3.weight"), 2 * D, w.GG, 2 * D));
+    LG_HIP(bn_train_bwd_sets(y.H1, 2 * D, w.GG, 2 * D, rows_of, 2 * D, y.ST, P.w(p + ".mlp.1.weight"),
                              P.w(p + ".mlp.1.bias"), w.GH, 2 * D, P.gr(p + ".mlp.1.weight"), P.gr(p + ".mlp.1.bias"), c.part,
                              sg_handle_sync(h), c.st));
     // the reference's checkpoint recomputation updates the running statistics again (:151-155)
     for (int set = 0; set < 2; ++set)
-      ST_HIP(bn_running_update(P.w(p + ".mlp.1.running_mean"), P.w(p + ".mlp.1.running_var"), y.ST + set * 6 * D, 2 * D,
+      LG_HIP(bn_running_update(P.w(p + ".mlp.1.running_mean"), P.w(p + ".mlp.1.running_var"), y.ST + set * 6 * D, 2 * D,
                                kMomentum, c.st));
     {  // dW = GH^T [x | message]: columns < 256 from x, the rest from CAT[:, 256:]
       float* dW = P.gr(p + ".mlp.0.weight");
@@ -489,23 +481,23 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
         g.ldb1 = 2 * D;
         g.N0 = D;
         g.colsumA = db;
-        ST_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
+        LG_HIP(tgemm(g, true, false, c.ws, c.ws_floats, c.st));
       } else if (db) {
-        ST_HIP(colsum(w.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st));
+        LG_HIP(colsum(w.GH, 2 * D, R, 2 * D, nullptr, c.part, db, c.st));
       }
     }
-    ST_HIP(linear_dgrad(c, w.GH, 2 * D, R, 2 * D, P.w(p + ".mlp.0.weight"), 2 * D, w.GC, 2 * D));
-    ST_HIP(add_rows256(GX, D, w.GC, 2 * D, GX2, D, R, c.st));  // residual + the mlp's x input
+    LG_HIP(linear_dgrad(c, w.GH, 2 * D, R, 2 * D, P.w(p + ".mlp.0.weight"), 2 * D, w.GC, 2 * D));
+    LG_HIP(add_rows256(GX, D, w.GC, 2 * D, GX2, D, R, c.st));  // residual + the mlp's x input
     // merge (head-major columns): d/d merge.weight gathered back to the reference's columns
     const float* gmsg = w.GC + D;
-    ST_HIP(linear_wgrad(c, gmsg, 2 * D, y.O, D, R, D, D, P.gr(p + ".attn.merge.weight") ? w.GW : nullptr,
+    LG_HIP(linear_wgrad(c, gmsg, 2 * D, y.O, D, R, D, D, P.gr(p + ".attn.merge.weight") ? w.GW : nullptr,
                         P.gr(p + ".attn.merge.bias")));
-    if (float* g = P.gr(p + ".attn.merge.weight")) ST_HIP(head_gather(w.GW, D, D, true, true, g, c.st));
-    ST_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, y.WM, D, w.GO, D));
+    if (float* g = P.gr(p + ".attn.merge.weight")) LG_HIP(head_gather(w.GW, D, D, true, true, g, c.st));
+    LG_HIP(linear_dgrad(c, gmsg, 2 * D, R, D, y.WM, D, w.GO, D));
     // attention backward
-    ST_HIP(attn_delta(y.O, w.GO, D, B, H, M, w.DELTA, c.st));
-    ST_HIP(attn_delta(y.O + o1 * D, w.GO + o1 * D, D, B, H, N, w.DELTA + lse1, c.st));
-    ST_HIP(hipMemsetAsync(w.GQKV, 0, (size_t)R * 3 * D * 4, c.st));
+    LG_HIP(attn_delta(y.O, w.GO, D, B, H, M, w.DELTA, c.st));
+    LG_HIP(attn_delta(y.O + o1 * D, w.GO + o1 * D, D, B, H, N, w.DELTA + lse1, c.st));
+    LG_HIP(hipMemsetAsync(w.GQKV, 0, (size_t)R * 3 * D * 4, c.st));
     const bool cross = d.type[l] == 1;
     for (int img = 0; img < 2; ++img) {
       const size_t qrow = img ? o1 : 0, krow = cross ? (img ? 0 : o1) : qrow;
@@ -517,10 +509,10 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
       a.dK = w.GQKV + krow * 3 * D + D;
       a.dV = w.GQKV + krow * 3 * D + 2 * D;
       a.accum_kv = 0;
-      ST_HIP(tattn_backward(a, c.st));
+      LG_HIP(tattn_backward(a, c.st));
     }
     // projections: d/d (head-major) weight and bias, scattered back per projection
-    ST_HIP(linear_wgrad(c, w.GQKV, 3 * D, X, D, R, 3 * D, D, w.GW, w.GB));
+    LG_HIP(linear_wgrad(c, w.GQKV, 3 * D, X, D, R, 3 * D, D, w.GW, w.GB));
     {
       HeadGathers hg;
       for (int t = 0; t < 3; ++t) {
@@ -528,15 +520,15 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
         if (float* g = P.gr(pj + ".weight")) hg.add(w.GW + (size_t)t * D * D, D, D, false, true, g);
         if (float* g = P.gr(pj + ".bias")) hg.add(w.GB + t * D, D, 1, false, true, g);
       }
-      ST_HIP(head_gather_multi(hg, c.st));
+      LG_HIP(head_gather_multi(hg, c.st));
     }
     sg_handle_grad_ready(h, l, stream);  // gnn.layers.<l>.* are final
-    ST_HIP(linear_dgrad(c, w.GQKV, 3 * D, R, 3 * D, y.WQKV, D, GX2, D, 1.f));
+    LG_HIP(linear_dgrad(c, w.GQKV, 3 * D, R, 3 * D, y.WQKV, D, GX2, D, 1.f));
     std::swap(GX, GX2);
   }
   // GX = d/d (desc + kenc(...)): the descriptors' gradient and the keypoint encoder's
-  if (grad_desc0) ST_HIP(hipMemcpyAsync(grad_desc0, GX, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
-  if (grad_desc1) ST_HIP(hipMemcpyAsync(grad_desc1, GX + o1 * D, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
+  if (grad_desc0) LG_HIP(hipMemcpyAsync(grad_desc0, GX, o1 * D * 4, hipMemcpyDeviceToDevice, c.st));
+  if (grad_desc1) LG_HIP(hipMemcpyAsync(grad_desc1, GX + o1 * D, (size_t)(R - R0) * D * 4, hipMemcpyDeviceToDevice, c.st));
   const int nk = (int)d.ch.size() - 1;
   const float* dY = GX;  // d/d (conv i output)
   long long lddy = D;
@@ -546,15 +538,15 @@ int sg_train_backward(sg_handle_t* h, float* const* params, const sg_inputs_t* i
     const std::string cv = conv_name("kenc.encoder", 3 * (i - 1));
     const int Ci = d.ch[i], Cp = d.ch[i - 1];
     const float* xin = i == 1 ? s.KIN : s.enc[i - 2].G;
-    ST_HIP(linear_wgrad(c, dY, lddy, xin, Cp, R, Ci, Cp, P.gr(cv + ".weight"), P.gr(cv + ".bias")));
+    LG_HIP(linear_wgrad(c, dY, lddy, xin, Cp, R, Ci, Cp, P.gr(cv + ".weight"), P.gr(cv + ".bias")));
     if (i == 1) break;  // the keypoints take no gradient
     float* gG = bufs[nb];
     float* gA = bufs[nb ^ 1];
     nb ^= 1;
-    ST_HIP(linear_dgrad(c, dY, lddy, R, Ci, P.w(cv + ".weight"), Cp, gG, Cp));
+    LG_HIP(linear_dgrad(c, dY, lddy, R, Ci, P.w(cv + ".weight"), Cp, gG, Cp));
     const Enc& e = s.enc[i - 2];
     const std::string bn = conv_name("kenc.encoder", 3 * (i - 2) + 1);
-    ST_HIP(bn_train_bwd_sets(e.A, Cp, gG, Cp, rows_of, Cp, e.ST, P.w(bn + ".weight"), P.w(bn + ".bias"), gA, Cp,
+    LG_HIP(bn_train_bwd_sets(e.A, Cp, gG, Cp, rows_of, Cp, e.ST, P.w(bn + ".weight"), P.w(bn + ".bias"), gA, Cp,
                              P.gr(bn + ".weight"), P.gr(bn + ".bias"), c.part, sg_handle_sync(h), c.st));
     dY = gA;
     lddy = Cp;
@@ -571,7 +563,7 @@ int sg_nll_backward(const float* stats, const float* grad_nll, const float* grad
       (mode != 0 && mode != 1))
     return fail(LG_E_INVALID, "bad argument");
   if (mode == 1 && M != N) return fail(LG_E_INVALID, "NLLLoss needs M == N (losses.py:72)");
-  ST_HIP(sg_nll_grad(gt_assignment, gt_matches0, gt_matches1, stats, grad_nll, grad_nll_pos, grad_nll_neg, B, M, N, mode,
+  LG_HIP(sg_nll_grad(gt_assignment, gt_matches0, gt_matches1, stats, grad_nll, grad_nll_pos, grad_nll_neg, B, M, N, mode,
                      nll_balancing, grad_log_assignment, (hipStream_t)stream));
   return LG_OK;
 }

@@ -10,24 +10,13 @@
 #include <string>
 
 #include "../../include/lightglue_mi355x.h"
+#include "api_common.h"
 #include "kernels.h"
 
 #include "common.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
 using namespace lg;
-
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define SPC_HIP(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int kSlots = 4;  // 0: max|x|; 1: the input image; 2: the output image
 enum { S_IN = 0, S_X = 1, S_Y = 2 };
@@ -134,46 +123,46 @@ int sp_conv_layer(const sp_conv_layer_args_t* args, void* workspace, size_t work
   _Float16* yp = static_cast<_Float16*>(a.y_planes);
   const long long yps = (long long)L.rpy * Cout;
 
-  SPC_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
-  SPC_HIP(hipMemsetAsync(stats, 0, 16 * sizeof(float), st));
-  SPC_HIP(range_absmax(a.x, (size_t)L.rin * Cin, rtab, S_IN, st));
+  LG_HIP(hipMemsetAsync(rtab, 0, (size_t)kSlots * kRangeStride * sizeof(unsigned), st));
+  LG_HIP(hipMemsetAsync(stats, 0, 16 * sizeof(float), st));
+  LG_HIP(range_absmax(a.x, (size_t)L.rin * Cin, rtab, S_IN, st));
   // stats: [0] max|W| of the repacked matrix; [1, 2] its largest row L1 norm, max|bias|; [3, 4] max|s|, max|t|
   const float* wmat = a.w;  // conv1a: [64][1][3][3] is already [64][9]
   if (!a.conv1a) {
     float* wrep = reinterpret_cast<float*>(ws + L.wrep);
-    SPC_HIP(sp_repack_conv(a.w, Cout, Cin, 3, wrep, st));
-    SPC_HIP(absmax(wrep, (size_t)Cout * 9 * Cin, stats, st));
+    LG_HIP(sp_repack_conv(a.w, Cout, Cin, 3, wrep, st));
+    LG_HIP(absmax(wrep, (size_t)Cout * 9 * Cin, stats, st));
     wmat = wrep;
   }
-  SPC_HIP(weight_range_stats(wmat, Cout, a.conv1a ? 9 : 9 * Cin, a.bias, stats + 1, st));
+  LG_HIP(weight_range_stats(wmat, Cout, a.conv1a ? 9 : 9 * Cin, a.bias, stats + 1, st));
   if (aff) {
-    SPC_HIP(absmax(a.post_scale, (size_t)Cout, stats + 3, st));
-    SPC_HIP(absmax(a.post_shift, (size_t)Cout, stats + 4, st));
+    LG_HIP(absmax(a.post_scale, (size_t)Cout, stats + 3, st));
+    LG_HIP(absmax(a.post_shift, (size_t)Cout, stats + 4, st));
   }
   float hs[16];
-  SPC_HIP(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, st));
-  SPC_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
   // |relu(conv + b)| <= g M[in] + bmax; with the affine |relu(.) s + t| <= max|s| (g M + bmax) + max|t|
   const float g = hs[1], bmax = hs[2], smax = aff ? hs[3] : 1.f, tmax = aff ? hs[4] : 0.f;
   const int in_slot = a.conv1a ? S_IN : S_X;  // gray weights sum to 1: |gray| <= max|image|
   const RangeOut ro{rtab, in_slot, -1, smax * g, 0.f, smax * bmax + tmax, S_Y, kRangeTrack};
 
   if (a.conv1a) {
-    SPC_HIP(sp_conv1a(a.x, B, Cin, H, W, a.w, a.bias, a.post_scale, a.post_shift, yp, L.rpy, ro, st));
+    LG_HIP(sp_conv1a(a.x, B, Cin, H, W, a.w, a.bias, a.post_scale, a.post_shift, yp, L.rpy, ro, st));
   } else {
     _Float16* xp = reinterpret_cast<_Float16*>(ws + L.xp);
     _Float16* wp = reinterpret_cast<_Float16*>(ws + L.wp);
     // the input image: two-sided exponent from max|x| (an input of any magnitude keeps 22 bits)
-    SPC_HIP(rows_to_planes(a.x, (int)L.rin, Cin, Cin, xp, L.rpx, 0,
-                           RangeOut{rtab, S_IN, -1, 1.f, 0.f, 0.f, S_X, kRangeTrack | kRangeTwoSided}, st));
-    SPC_HIP(sp_zero_rows(xp, (long long)L.rpx * Cin, L.rpx, Cin, (int)L.rin, st));
+    LG_HIP(rows_to_planes(a.x, (int)L.rin, Cin, Cin, xp, L.rpx, 0,
+                          RangeOut{rtab, S_IN, -1, 1.f, 0.f, 0.f, S_X, kRangeTrack | kRangeTwoSided}, st));
+    LG_HIP(sp_zero_rows(xp, (long long)L.rpx * Cin, L.rpx, Cin, (int)L.rin, st));
     int sw = 0;
     if (hs[0] > 0.f && std::isfinite(hs[0])) {
       int E;
       (void)std::frexp(hs[0], &E);  // max = m 2^E, m in [0.5, 1)
       sw = std::min(std::max(4 - E, -100), 100);
     }
-    SPC_HIP(split_weight_h3(wmat, Cout, 9 * Cin, std::ldexp(1.f, sw), wp, st));
+    LG_HIP(split_weight_h3(wmat, Cout, 9 * Cin, std::ldexp(1.f, sw), wp, st));
     ConvH3Args c{};
     c.X = {xp, (long long)L.rpx * Cin, L.rpx};
     c.B = B;
@@ -193,12 +182,12 @@ int sp_conv_layer(const sp_conv_layer_args_t* args, void* workspace, size_t work
     c.pool = a.pool ? 1 : 0;
     c.post_scale = a.post_scale;
     c.post_shift = a.post_shift;
-    SPC_HIP(sp_conv3x3(c, st));
+    LG_HIP(sp_conv3x3(c, st));
   }
-  if (a.y_rows) SPC_HIP(image_to_rows(yp, yps, L.rpy, Cout, a.y_rows, (int)L.rout, rtab, S_Y, st));
+  if (a.y_rows) LG_HIP(image_to_rows(yp, yps, L.rpy, Cout, a.y_rows, (int)L.rout, rtab, S_Y, st));
   unsigned htab[kSlots * kRangeStride];
-  SPC_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
-  SPC_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipMemcpyAsync(htab, rtab, sizeof(htab), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
   if (a.exp_in) *a.exp_in = a.conv1a ? 0 : tab_exp(htab, S_X);
   if (a.exp_out) *a.exp_out = tab_exp(htab, S_Y);
   if (a.max_out) *a.max_out = tab_max(htab, S_Y);
@@ -210,7 +199,7 @@ int sp_head_scores(const float* logits, int32_t ld, int32_t B, int32_t Hc, int32
   if (B <= 0 || Hc <= 0 || Wc <= 0 || ld < 65 || (int64_t)B * Hc * Wc * 64 >= (1LL << 31))
     return fail(LG_E_INVALID, "bad shape (B, Hc, Wc > 0, ld >= 65, B * Hc * Wc * 64 < 2^31)");
   if (off16(scores)) return fail(LG_E_INVALID, "scores is not 16-byte aligned");
-  SPC_HIP(sp_detector_scores(logits, ld, B, Hc, Wc, scores, (hipStream_t)stream));
+  LG_HIP(sp_detector_scores(logits, ld, B, Hc, Wc, scores, (hipStream_t)stream));
   return LG_OK;
 }
 
@@ -218,7 +207,7 @@ int sp_head_normalize(const float* x, int32_t rows, float* y, void* stream) {
   if (!x || !y) return fail(LG_E_INVALID, "null argument");
   if (rows <= 0) return fail(LG_E_INVALID, "rows must be positive");
   if (off16(x) || off16(y)) return fail(LG_E_INVALID, "a pointer is not 16-byte aligned");
-  SPC_HIP(sp_desc_normalize(x, rows, y, (hipStream_t)stream));
+  LG_HIP(sp_desc_normalize(x, rows, y, (hipStream_t)stream));
   return LG_OK;
 }
 

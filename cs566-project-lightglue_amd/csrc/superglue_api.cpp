@@ -18,50 +18,33 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/lightglue_mi355x.h"
 #include "../../include/superglue_mi355x.h"
+#include "api_common.h"
 #include "common.h"
 #include "kernels.h"
 #include "train.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
-
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define SG_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int D = 256, H = 4, HD = 64;
 constexpr int kSlots = 512;
 // per forward: at most 6 slots for the encoder / inputs, 4 per GNN layer, 1 for the head
 static_assert(kSlots >= 8 + 4 * SG_MAX_LAYERS, "range table too small for SG_MAX_LAYERS");
 
-struct Tensor {
-  std::string name;
-  int64_t numel;
-};
-
 // MLP (superglue.py:63-72) schema: conv weights / biases and BatchNorm tensors (no counters)
-void add_mlp(std::vector<Tensor>& s, const std::string& p, const std::vector<int>& ch) {
+void add_mlp(lg::WeightSchema& s, const std::string& p, const std::vector<int>& ch) {
   int idx = 0;
   for (size_t i = 1; i < ch.size(); ++i) {
-    s.push_back({p + "." + std::to_string(idx) + ".weight", (int64_t)ch[i] * ch[i - 1]});
-    s.push_back({p + "." + std::to_string(idx) + ".bias", ch[i]});
+    s.add(p + "." + std::to_string(idx) + ".weight", (int64_t)ch[i] * ch[i - 1]);
+    s.add(p + "." + std::to_string(idx) + ".bias", ch[i]);
     ++idx;
     if (i < ch.size() - 1) {
       for (const char* f : {"weight", "bias", "running_mean", "running_var"})
-        s.push_back({p + "." + std::to_string(idx) + "." + f, ch[i]});
+        s.add(p + "." + std::to_string(idx) + "." + f, ch[i]);
       idx += 2;
     }
   }
@@ -74,21 +57,22 @@ std::vector<int> kenc_channels(const sg_config_t& c) {
   return ch;
 }
 
-std::vector<Tensor> make_schema(const sg_config_t& c) {
-  std::vector<Tensor> s = {{"bin_score", 1}};  // the module's own parameter leads its state dict
+lg::WeightSchema make_schema(const sg_config_t& c) {
+  lg::WeightSchema s;
+  s.add("bin_score", 1);  // the module's own parameter leads its state dict
   add_mlp(s, "kenc.encoder", kenc_channels(c));
   for (int i = 0; i < c.n_layers; ++i) {
     const std::string p = "gnn.layers." + std::to_string(i);
-    s.push_back({p + ".attn.merge.weight", (int64_t)D * D});
-    s.push_back({p + ".attn.merge.bias", D});
+    s.add(p + ".attn.merge.weight", (int64_t)D * D);
+    s.add(p + ".attn.merge.bias", D);
     for (int j = 0; j < 3; ++j) {
-      s.push_back({p + ".attn.proj." + std::to_string(j) + ".weight", (int64_t)D * D});
-      s.push_back({p + ".attn.proj." + std::to_string(j) + ".bias", D});
+      s.add(p + ".attn.proj." + std::to_string(j) + ".weight", (int64_t)D * D);
+      s.add(p + ".attn.proj." + std::to_string(j) + ".bias", D);
     }
     add_mlp(s, p + ".mlp", {2 * D, 2 * D, D});
   }
-  s.push_back({"final_proj.weight", (int64_t)D * D});
-  s.push_back({"final_proj.bias", D});
+  s.add("final_proj.weight", (int64_t)D * D);
+  s.add("final_proj.bias", D);
   return s;
 }
 
@@ -158,8 +142,7 @@ struct sg_handle {
   lg::BnSync sync;                          // sg_set_collective (SyncBatchNorm across ranks)
   sg_grad_ready_fn grad_hook = nullptr;     // sg_set_grad_ready_hook
   void* grad_hook_ctx = nullptr;
-  std::vector<Tensor> schema;
-  std::map<std::string, int> index;
+  lg::WeightSchema schema;
   std::vector<float*> raw;   // device copies of the loaded tensors (schema order)
   float* buf = nullptr;      // packed / folded fp32 weights
   int* perm = nullptr;       // qkv_perm [768] | merge_perm [256]
@@ -201,10 +184,7 @@ const BnSync* sg_handle_sync(const sg_handle* h) { return h->sync.fn ? &h->sync 
 void sg_handle_grad_ready(const sg_handle* h, int layer, void* stream) {
   if (h->grad_hook) h->grad_hook(h->grad_hook_ctx, layer, stream);
 }
-int sg_handle_weight_index(const sg_handle* h, const std::string& name) {
-  auto it = h->index.find(name);
-  return it == h->index.end() ? -1 : it->second;
-}
+const WeightSchema& sg_handle_schema(const sg_handle* h) { return h->schema; }
 }  // namespace lg
 
 extern "C" {
@@ -220,12 +200,11 @@ int sg_create(const sg_config_t* cfg, int device, sg_handle_t** out) {
   for (int i = 0; i < cfg->n_layers; ++i)
     if (cfg->layer_types[i] != 0 && cfg->layer_types[i] != 1) return fail(LG_E_INVALID, "GNN layer must be self or cross");
   if (cfg->sinkhorn_iterations < 0) return fail(LG_E_INVALID, "num_sinkhorn_iterations must be >= 0");
-  SG_HIP(hipSetDevice(device));
+  LG_HIP(hipSetDevice(device));
   sg_handle* h = new sg_handle();
   h->cfg = *cfg;
   h->device = device;
   h->schema = make_schema(*cfg);
-  for (size_t k = 0; k < h->schema.size(); ++k) h->index[h->schema[k].name] = (int)k;
   h->ch = kenc_channels(*cfg);
   h->enc_gemm = h->ch.size() >= 3 && h->ch[h->ch.size() - 2] % 32 == 0;
   *out = h;
@@ -243,40 +222,26 @@ int sg_destroy(sg_handle_t* h) {
   return LG_OK;
 }
 
-int sg_weight_count(const sg_handle_t* h) { return h ? (int)h->schema.size() : 0; }
-const char* sg_weight_name(const sg_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].name.c_str() : nullptr;
-}
-int64_t sg_weight_numel(const sg_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].numel : -1;
-}
+int sg_weight_count(const sg_handle_t* h) { return h ? lg::weight_count(h->schema) : 0; }
+const char* sg_weight_name(const sg_handle_t* h, int i) { return h ? lg::weight_name(h->schema, i) : nullptr; }
+int64_t sg_weight_numel(const sg_handle_t* h, int i) { return h ? lg::weight_numel(h->schema, i) : -1; }
 
 int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float* const* tensors, const int64_t* numels,
                     void* stream) {
   if (!h || n < 0 || (n && (!names || !tensors || !numels))) return fail(LG_E_INVALID, "null argument");
-  SG_HIP(hipSetDevice(h->device));
+  LG_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int> seen(h->schema.size(), 0), src(h->schema.size(), -1);
-  for (int i = 0; i < n; ++i) {
-    auto it = h->index.find(names[i]);
-    if (it == h->index.end()) return fail(LG_E_WEIGHTS, std::string("unexpected key in state_dict: ") + names[i]);
-    const int k = it->second;
-    if (seen[k]++) return fail(LG_E_WEIGHTS, std::string("duplicate key: ") + names[i]);
-    if (numels[i] != h->schema[k].numel)
-      return fail(LG_E_WEIGHTS, std::string("size mismatch for ") + names[i] + ": expected " +
-                                    std::to_string(h->schema[k].numel) + " got " + std::to_string(numels[i]));
-    src[k] = i;
-  }
-  for (size_t k = 0; k < h->schema.size(); ++k)
-    if (!seen[k]) return fail(LG_E_WEIGHTS, "missing key in state_dict: " + h->schema[k].name);
+  std::vector<int> src;
+  std::string err;
+  if (!h->schema.match(n, names, tensors, numels, src, err)) return fail(LG_E_WEIGHTS, err);
   // raw device copies (BatchNorm statistics and the encoder are read from them directly)
   for (float* p : h->raw) (void)hipFree(p);
   h->raw.assign(h->schema.size(), nullptr);
-  for (size_t k = 0; k < h->schema.size(); ++k) {
-    SG_HIP(hipMalloc((void**)&h->raw[k], h->schema[k].numel * sizeof(float)));
-    SG_HIP(hipMemcpyAsync(h->raw[k], tensors[src[k]], h->schema[k].numel * sizeof(float), hipMemcpyDeviceToDevice, st));
+  for (int k = 0; k < h->schema.size(); ++k) {
+    LG_HIP(hipMalloc((void**)&h->raw[k], h->schema.numel(k) * sizeof(float)));
+    LG_HIP(hipMemcpyAsync(h->raw[k], tensors[src[k]], h->schema.numel(k) * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  auto raw = [&](const std::string& name) { return h->raw[h->index.at(name)]; };
+  auto raw = [&](const std::string& name) { return h->raw[h->schema.find(name)]; };
 
   // packed layout
   const int L = h->cfg.n_layers;
@@ -291,7 +256,7 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
     sg_handle::Enc e;
     e.wt = take((size_t)h->ch[l] * h->ch[l + 1]);
     e.b = take(h->ch[l + 1]);
-    e.bn = l + 2 < h->ch.size() ? h->index.at("kenc.encoder." + std::to_string(3 * l + 1) + ".weight") : -1;
+    e.bn = l + 2 < h->ch.size() ? h->schema.find("kenc.encoder." + std::to_string(3 * l + 1) + ".weight") : -1;
     h->enc.push_back(e);
   }
   h->layers.assign(L, {});
@@ -308,20 +273,20 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
   float* tmp = nullptr;
   if (h->buf) (void)hipFree(h->buf);
   h->buf = nullptr;
-  SG_HIP(hipMalloc((void**)&h->buf, off * sizeof(float)));
+  LG_HIP(hipMalloc((void**)&h->buf, off * sizeof(float)));
   if (!h->perm) {
-    SG_HIP(hipMalloc((void**)&h->perm, 4 * D * sizeof(int)));
+    LG_HIP(hipMalloc((void**)&h->perm, 4 * D * sizeof(int)));
     std::vector<int> p = qkv_perm(), pm = merge_perm();
     p.insert(p.end(), pm.begin(), pm.end());
-    SG_HIP(hipMemcpy(h->perm, p.data(), p.size() * sizeof(int), hipMemcpyHostToDevice));
+    LG_HIP(hipMemcpy(h->perm, p.data(), p.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  SG_HIP(hipMallocAsync((void**)&tmp, (3 * D * D + 3 * D + 512 * 256 + 512 + D * D) * sizeof(float), st));
+  LG_HIP(hipMallocAsync((void**)&tmp, (3 * D * D + 3 * D + 512 * 256 + 512 + D * D) * sizeof(float), st));
   float* B = h->buf;
   // keypoint encoder: transposed weights
   for (size_t l = 0; l < h->enc.size(); ++l) {
     const std::string p = "kenc.encoder." + std::to_string(3 * l);
-    SG_HIP(lg::sg_transpose(raw(p + ".weight"), h->ch[l + 1], h->ch[l], B + h->enc[l].wt, st));
-    SG_HIP(hipMemcpyAsync(B + h->enc[l].b, raw(p + ".bias"), h->ch[l + 1] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(lg::sg_transpose(raw(p + ".weight"), h->ch[l + 1], h->ch[l], B + h->enc[l].wt, st));
+    LG_HIP(hipMemcpyAsync(B + h->enc[l].b, raw(p + ".bias"), h->ch[l + 1] * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   for (int i = 0; i < L; ++i) {
     sg_handle::Layer& ly = h->layers[i];
@@ -331,31 +296,31 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
     float* stb = tmp + 3 * D * D;
     for (int j = 0; j < 3; ++j) {
       const std::string q = p + ".attn.proj." + std::to_string(j);
-      SG_HIP(hipMemcpyAsync(stk + (size_t)j * D * D, raw(q + ".weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-      SG_HIP(hipMemcpyAsync(stb + j * D, raw(q + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+      LG_HIP(hipMemcpyAsync(stk + (size_t)j * D * D, raw(q + ".weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+      LG_HIP(hipMemcpyAsync(stb + j * D, raw(q + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    SG_HIP(lg::gather_rows(B + ly.qkv.off, stk, h->perm, 3 * D, D, st));
-    SG_HIP(lg::gather_rows(B + ly.qkv.boff, stb, h->perm, 3 * D, 1, st));
+    LG_HIP(lg::gather_rows(B + ly.qkv.off, stk, h->perm, 3 * D, D, st));
+    LG_HIP(lg::gather_rows(B + ly.qkv.boff, stb, h->perm, 3 * D, 1, st));
     // merge columns into context order, folded into mlp.0 (fold_out_proj: W1[:, 256:] Wm, b1 +=
     // W1[:, 256:] bm), then the eval BatchNorm of mlp.1
     float* wm = tmp + 3 * D * D + 3 * D + 512 * 256 + 512;
-    SG_HIP(lg::sg_gather_cols(wm, raw(p + ".attn.merge.weight"), h->perm + 3 * D, D, D, st));
-    SG_HIP(hipMemcpyAsync(B + ly.w1.off, raw(p + ".mlp.0.weight"), 4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SG_HIP(hipMemcpyAsync(B + ly.w1.boff, raw(p + ".mlp.0.bias"), 2 * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SG_HIP(lg::fold_out_proj(B + ly.w1.off, B + ly.w1.boff, wm, raw(p + ".attn.merge.bias"), tmp + 3 * D * D + 3 * D, st));
-    SG_HIP(lg::sg_bn_fold(B + ly.w1.off, B + ly.w1.boff, raw(p + ".mlp.1.weight"), raw(p + ".mlp.1.bias"),
+    LG_HIP(lg::sg_gather_cols(wm, raw(p + ".attn.merge.weight"), h->perm + 3 * D, D, D, st));
+    LG_HIP(hipMemcpyAsync(B + ly.w1.off, raw(p + ".mlp.0.weight"), 4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(B + ly.w1.boff, raw(p + ".mlp.0.bias"), 2 * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(lg::fold_out_proj(B + ly.w1.off, B + ly.w1.boff, wm, raw(p + ".attn.merge.bias"), tmp + 3 * D * D + 3 * D, st));
+    LG_HIP(lg::sg_bn_fold(B + ly.w1.off, B + ly.w1.boff, raw(p + ".mlp.1.weight"), raw(p + ".mlp.1.bias"),
                           raw(p + ".mlp.1.running_mean"), raw(p + ".mlp.1.running_var"), 2 * D, 2 * D, st));
-    SG_HIP(hipMemcpyAsync(B + ly.w2.off, raw(p + ".mlp.3.weight"), 2 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SG_HIP(hipMemcpyAsync(B + ly.w2.boff, raw(p + ".mlp.3.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(B + ly.w2.off, raw(p + ".mlp.3.weight"), 2 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(B + ly.w2.boff, raw(p + ".mlp.3.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   if (h->enc_gemm) {
     const std::string p = "kenc.encoder." + std::to_string(3 * (h->ch.size() - 2));
-    SG_HIP(hipMemcpyAsync(B + h->enc_last.off, raw(p + ".weight"), (size_t)D * kl * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SG_HIP(hipMemcpyAsync(B + h->enc_last.boff, raw(p + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(B + h->enc_last.off, raw(p + ".weight"), (size_t)D * kl * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(B + h->enc_last.boff, raw(p + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  SG_HIP(hipMemcpyAsync(B + h->fin.off, raw("final_proj.weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  SG_HIP(hipMemcpyAsync(B + h->fin.boff, raw("final_proj.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  SG_HIP(hipFreeAsync(tmp, st));
+  LG_HIP(hipMemcpyAsync(B + h->fin.off, raw("final_proj.weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  LG_HIP(hipMemcpyAsync(B + h->fin.boff, raw("final_proj.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  LG_HIP(hipFreeAsync(tmp, st));
 
   // fp16x3 plane images (per-matrix power-of-two scale, max |W 2^sw| in [8, 16)) and range stats
   std::vector<sg_handle::Mat*> mats;
@@ -370,25 +335,25 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
   for (auto* m : mats) total += 2 * (size_t)m->rows * m->K;
   if (h->planes) (void)hipFree(h->planes);
   h->planes = nullptr;
-  SG_HIP(hipMalloc((void**)&h->planes, total * sizeof(_Float16)));
+  LG_HIP(hipMalloc((void**)&h->planes, total * sizeof(_Float16)));
   const size_t nst = mats.size() * 3 + 4 * (size_t)L + 1;
   float* dst = nullptr;
-  SG_HIP(hipMallocAsync((void**)&dst, nst * sizeof(float), st));
+  LG_HIP(hipMallocAsync((void**)&dst, nst * sizeof(float), st));
   for (size_t i = 0; i < mats.size(); ++i) {
-    SG_HIP(lg::absmax(B + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
-    SG_HIP(lg::weight_range_stats(B + mats[i]->off, mats[i]->rows, mats[i]->K, B + mats[i]->boff, dst + 3 * i + 1, st));
+    LG_HIP(lg::absmax(B + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
+    LG_HIP(lg::weight_range_stats(B + mats[i]->off, mats[i]->rows, mats[i]->K, B + mats[i]->boff, dst + 3 * i + 1, st));
   }
   float* ls = dst + 3 * mats.size();
   for (int i = 0; i < L; ++i) {
     const auto& q = h->layers[i].qkv;
-    SG_HIP(lg::weight_range_stats(B + q.off + (size_t)D * D, D, D, B + q.boff + D, ls + 4 * i, st));
-    SG_HIP(lg::weight_range_stats(B + q.off + (size_t)2 * D * D, D, D, B + q.boff + 2 * D, ls + 4 * i + 2, st));
+    LG_HIP(lg::weight_range_stats(B + q.off + (size_t)D * D, D, D, B + q.boff + D, ls + 4 * i, st));
+    LG_HIP(lg::weight_range_stats(B + q.off + (size_t)2 * D * D, D, D, B + q.boff + 2 * D, ls + 4 * i + 2, st));
   }
-  SG_HIP(hipMemcpyAsync(ls + 4 * L, raw("bin_score"), sizeof(float), hipMemcpyDeviceToDevice, st));
+  LG_HIP(hipMemcpyAsync(ls + 4 * L, raw("bin_score"), sizeof(float), hipMemcpyDeviceToDevice, st));
   std::vector<float> hs(nst);
-  SG_HIP(hipMemcpyAsync(hs.data(), dst, nst * sizeof(float), hipMemcpyDeviceToHost, st));
-  SG_HIP(hipStreamSynchronize(st));
-  SG_HIP(hipFreeAsync(dst, st));
+  LG_HIP(hipMemcpyAsync(hs.data(), dst, nst * sizeof(float), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipFreeAsync(dst, st));
   size_t poff = 0;
   for (size_t i = 0; i < mats.size(); ++i) {
     sg_handle::Mat& m = *mats[i];
@@ -399,7 +364,7 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
       (void)std::frexp(mx, &E);
       sw = std::min(std::max(4 - E, -100), 100);
     }
-    SG_HIP(lg::split_weight_h3(B + m.off, m.rows, m.K, std::ldexp(1.f, sw), h->planes + poff, st));
+    LG_HIP(lg::split_weight_h3(B + m.off, m.rows, m.K, std::ldexp(1.f, sw), h->planes + poff, st));
     m.poff = poff;
     m.unscale = std::ldexp(1.f, -(11 + sw));
     m.g = hs[3 * i + 1];
@@ -413,7 +378,7 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
     h->layers[i].bV = hs[3 * mats.size() + 4 * i + 3];
   }
   h->bin_score = hs[3 * mats.size() + 4 * L];
-  SG_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipStreamSynchronize(st));
   h->loaded = true;
   return LG_OK;
 }
@@ -445,7 +410,7 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
     return fail(LG_E_INVALID, "missing output tensor");
   const Work need = carve(nullptr, B, M, N);
   if (!workspace || workspace_bytes < need.bytes) return fail(LG_E_WORKSPACE, "workspace too small: need " + std::to_string(need.bytes));
-  SG_HIP(hipSetDevice(h->device));
+  LG_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   Work w = carve((char*)workspace, B, M, N);
   const int R = B * (M + N), RP = w.rows_pad;
@@ -462,13 +427,13 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
     g.acc_scale = m.unscale;
     g.bias = W + m.boff;
   };
-  SG_HIP(hipMemsetAsync(rt, 0, kSlots * kRangeStride * sizeof(unsigned), st));
+  LG_HIP(hipMemsetAsync(rt, 0, kSlots * kRangeStride * sizeof(unsigned), st));
   const bool ragged = n0 != nullptr;
   const SegLayout SL{B, M, N};
   RowMask live{};  // cnt == null without counts: every row live
   const int *c0 = nullptr, *c1 = nullptr;
   if (ragged) {
-    SG_HIP(ragged_counts(SL, n0, n1, w.cnt, st));
+    LG_HIP(ragged_counts(SL, n0, n1, w.cnt, st));
     live = RowMask{w.cnt, nullptr, 1, SL};
     c0 = w.cnt;
     c1 = w.cnt + B;
@@ -481,8 +446,8 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
   const int nl_valu = h->enc_gemm ? nl_all - 1 : nl_all;
   const int kl = h->ch[nl_valu];
   if (h->enc_gemm) {
-    SG_HIP(hipMemcpyAsync(w.X, in->descriptors0, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
-    SG_HIP(hipMemcpyAsync(w.X + (size_t)B * M * D, in->descriptors1, sizeof(float) * B * N * D, hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(w.X, in->descriptors0, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(w.X + (size_t)B * M * D, in->descriptors1, sizeof(float) * B * N * D, hipMemcpyDeviceToDevice, st));
   }
   for (int s = 0; s < 2; ++s) {
     SgEncArgs e;
@@ -517,21 +482,21 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
         e.layer[l].bn_var = h->raw[h->enc[l].bn + 3];
       }
     }
-    SG_HIP(sg_keypoint_encoder(e, st));
+    LG_HIP(sg_keypoint_encoder(e, st));
   }
   int s_x = -1;
   if (h->enc_gemm) {
     const int s_d = slot(), s_hr = slot(), s_he = slot();
     s_x = slot();
     if (ragged) {  // real rows only: the padding must not reach the range table
-      SG_HIP(range_absmax_rows(in->descriptors0, B * M, D, D, 0, live, rt, s_d, st));
-      SG_HIP(range_absmax_rows(in->descriptors1, B * N, D, D, B * M, live, rt, s_d, st));
-      SG_HIP(range_absmax_rows(w.ctx, R, kl, kl, 0, live, rt, s_hr, st));
+      LG_HIP(range_absmax_rows(in->descriptors0, B * M, D, D, 0, live, rt, s_d, st));
+      LG_HIP(range_absmax_rows(in->descriptors1, B * N, D, D, B * M, live, rt, s_d, st));
+      LG_HIP(range_absmax_rows(w.ctx, R, kl, kl, 0, live, rt, s_hr, st));
     } else {
-      SG_HIP(range_absmax2(in->descriptors0, (size_t)B * M * D, in->descriptors1, (size_t)B * N * D, rt, s_d, st));
-      SG_HIP(range_absmax(w.ctx, (size_t)R * kl, rt, s_hr, st));
+      LG_HIP(range_absmax2(in->descriptors0, (size_t)B * M * D, in->descriptors1, (size_t)B * N * D, rt, s_d, st));
+      LG_HIP(range_absmax(w.ctx, (size_t)R * kl, rt, s_hr, st));
     }
-    SG_HIP(rows_to_planes(w.ctx, R, kl, kl, w.Hp, RP, 0, ro(s_hr, 1.f, -1, 0.f, 0.f, s_he, 1), st, nullptr,
+    LG_HIP(rows_to_planes(w.ctx, R, kl, kl, w.Hp, RP, 0, ro(s_hr, 1.f, -1, 0.f, 0.f, s_he, 1), st, nullptr,
                           ragged ? &live : nullptr));
     GemmH3Args g;
     memset(&g, 0, sizeof(g));
@@ -541,13 +506,13 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
     g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
     g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
     g.ro = ro(s_d, 1.f, s_he, h->enc_last.g, h->enc_last.bmax, s_x, 1);
-    SG_HIP(gemm_h3(g, EPI_STORE, st));
+    LG_HIP(gemm_h3(g, EPI_STORE, st));
   } else {
     const int s_in = slot();
     s_x = slot();
-    if (ragged) SG_HIP(range_absmax_rows(w.X, R, D, D, 0, live, rt, s_in, st));
-    else SG_HIP(range_absmax(w.X, (size_t)R * D, rt, s_in, st));
-    SG_HIP(rows_to_planes(w.X, R, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st, nullptr,
+    if (ragged) LG_HIP(range_absmax_rows(w.X, R, D, D, 0, live, rt, s_in, st));
+    else LG_HIP(range_absmax(w.X, (size_t)R * D, rt, s_in, st));
+    LG_HIP(rows_to_planes(w.X, R, D, D, w.Xp, RP, 0, ro(s_in, 1.f, -1, 0.f, 0.f, s_x, 1), st, nullptr,
                           ragged ? &live : nullptr));
   }
 
@@ -570,7 +535,7 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
       g.ro = ro(s_x, ly.gK, -1, 0.f, ly.bK, s_k, 1);
       g.ro_v = ro(s_x, ly.gV, -1, 0.f, ly.bV, s_v, kRangeTrack | kRangeTwoSided);  // M[v] bounds the context (mlp.0's input)
       g.R = R; g.Nout = 3 * D; g.hl = hl; g.rm = live;
-      SG_HIP(gemm_h3(g, EPI_QKV_ROT, st));
+      LG_HIP(gemm_h3(g, EPI_QKV_ROT, st));
     }
     {
       const void* kp1 = static_cast<const char*>(w.KP) + 2 * img1;
@@ -584,7 +549,7 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
         a0 = {w.Q, kp1, vp1, ps, w.ctx, M, N, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c1, nullptr};
         a1 = {w.Q + img1, w.KP, w.VP, ps, ctx1, N, M, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c0, nullptr};
       }
-      SG_HIP(attention_f32(a0, a1, B, H, 0.125f, PREC_H3, st));  // 1 / sqrt(dim = 64) (:108)
+      LG_HIP(attention_f32(a0, a1, B, H, 0.125f, PREC_H3, st));  // 1 / sqrt(dim = 64) (:108)
     }
     // mlp.0 with merge and BatchNorm folded, ReLU -> hidden plane image (context planes carry the
     // value planes' exponent, s_v)
@@ -598,7 +563,7 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
       g.R = R; g.Nout = 2 * D; g.relu = 1; g.rm = live;
       g.Yp = w.Hp; g.yps = (long long)RP * 2 * D; g.yrows_pad = RP;
       g.ro = ro(s_x, ly.w1.g, s_v, ly.w1.g, ly.w1.bmax, s_h, 1);
-      SG_HIP(gemm_h3(g, EPI_STORE, st));
+      LG_HIP(gemm_h3(g, EPI_STORE, st));
     }
     {  // mlp.3 + residual: x = x + delta (fp32 rows and plane image)
       GemmH3Args g;
@@ -609,15 +574,15 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
       g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
       g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
       g.ro = ro(s_x, 1.f, s_h, ly.w2.g, ly.w2.bmax, s_xn, 1);
-      SG_HIP(gemm_h3(g, EPI_STORE, st));
+      LG_HIP(gemm_h3(g, EPI_STORE, st));
     }
     s_x = s_xn;
   }
-  if (ragged) SG_HIP(zero_dead_rows(w.X, R, D, 0, live, st));  // padded rows leave as zeros, not stale workspace
+  if (ragged) LG_HIP(zero_dead_rows(w.X, R, D, 0, live, st));  // padded rows leave as zeros, not stale workspace
   if (out->descriptors0)
-    SG_HIP(hipMemcpyAsync(out->descriptors0, w.X, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(out->descriptors0, w.X, sizeof(float) * B * M * D, hipMemcpyDeviceToDevice, st));
   if (out->descriptors1)
-    SG_HIP(hipMemcpyAsync(out->descriptors1, w.X + (size_t)B * M * D, sizeof(float) * B * N * D, hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(out->descriptors1, w.X + (size_t)B * M * D, sizeof(float) * B * N * D, hipMemcpyDeviceToDevice, st));
 
   // ---- final_proj, cost = md0 . md1 / sqrt(256) (superglue.py:278-282), Sinkhorn, filter
   {
@@ -627,10 +592,10 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
     g.A0 = image(w.Xp, D); g.K0 = D; g.K = D; wplanes(g, h->fin);
     g.rtab = rt; g.a0_slot = s_x; g.a1_slot = -1;
     g.R = R; g.Nout = D; g.Y = w.md; g.ldy = D; g.rm = live;
-    SG_HIP(gemm_h3(g, EPI_STORE, st));
+    LG_HIP(gemm_h3(g, EPI_STORE, st));
   }
   // zero md rows of the padding: the cost is then 0 (and finite) outside the pair's real block
-  if (ragged) SG_HIP(zero_dead_rows(w.md, R, D, 0, live, st));
+  if (ragged) LG_HIP(zero_dead_rows(w.md, R, D, 0, live, st));
   float* cost = out->sinkhorn_cost ? out->sinkhorn_cost : w.cost;
   {
     GemmArgs g;
@@ -639,11 +604,11 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
     g.W = w.md + (size_t)B * M * D; g.ldw = D; g.sW = (long long)N * D;
     g.R = M; g.Nout = N; g.Y = cost; g.ldy = N; g.sY = (long long)M * N;
     g.out_scale = 1.f / 16.f;
-    SG_HIP(gemm_x6(g, EPI_STORE, B, st));
+    LG_HIP(gemm_x6(g, EPI_STORE, B, st));
   }
   float* Z = out->log_assignment ? out->log_assignment : w.Z;
-  SG_HIP(log_optimal_transport(cost, h->bin_score, B, M, N, h->cfg.sinkhorn_iterations, Z, w.sws, st, c0, c1));
-  SG_HIP(filter_from_scores(Z, B, M, N, h->cfg.filter_threshold, w.fws, out->matches0, out->matches1,
+  LG_HIP(log_optimal_transport(cost, h->bin_score, B, M, N, h->cfg.sinkhorn_iterations, Z, w.sws, st, c0, c1));
+  LG_HIP(filter_from_scores(Z, B, M, N, h->cfg.filter_threshold, w.fws, out->matches0, out->matches1,
                             out->matching_scores0, out->matching_scores1, st, ragged ? w.cnt : nullptr));
   return LG_OK;
 }
@@ -668,7 +633,7 @@ static int nll_loss(const float* la, int32_t B, int32_t M, int32_t N, const uint
   if (mode == 1 && M != N)  // losses.py:72 writes gt_matches1 == -1 into [:, -1, :m]
     return fail(LG_E_INVALID, "The expanded size of the tensor (" + std::to_string(M) +
                                   ") must match the existing size (" + std::to_string(N) + ") at non-singleton dimension 1");
-  SG_HIP(lg::sg_nll_loss(la, B, M, N, gta, gt0, gt1, mode, bal, out, static_cast<double*>(ws), (hipStream_t)stream));
+  LG_HIP(lg::sg_nll_loss(la, B, M, N, gta, gt0, gt1, mode, bal, out, static_cast<double*>(ws), (hipStream_t)stream));
   return LG_OK;
 }
 

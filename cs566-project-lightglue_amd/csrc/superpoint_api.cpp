@@ -7,41 +7,19 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/lightglue_mi355x.h"
 #include "../../include/superpoint_mi355x.h"
+#include "api_common.h"
 #include "common.h"
 #include "kernels.h"
 
-namespace lg {
-int api_fail(int code, const char* msg);
-}
-
 namespace {
 
-int fail(int code, const std::string& msg) { return lg::api_fail(code, msg.c_str()); }
-
-#define SP_HIP(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(LG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-struct Tensor {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t numel() const {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    return n;
-  }
-};
-
 // superpoint.py:179-196, registration order (lightglue_amd.sp_weights.superpoint_schema)
-std::vector<Tensor> make_schema(const sp_config_t& c) {
+lg::WeightSchema make_schema(const sp_config_t& c) {
   struct L { const char* n; int ci, co, k; };
   std::vector<L> ls = {{"conv1a", 1, 64, 3},    {"conv1b", 64, 64, 3},   {"conv2a", 64, 64, 3},
                        {"conv2b", 64, 64, 3},   {"conv3a", 64, 128, 3},  {"conv3b", 128, 128, 3},
@@ -54,10 +32,10 @@ std::vector<Tensor> make_schema(const sp_config_t& c) {
     ls.push_back({"convDa", 128, 256, 3});
     ls.push_back({"convDb", 256, c.descriptor_dim, 1});
   }
-  std::vector<Tensor> s;
+  lg::WeightSchema s;
   for (auto& l : ls) {
-    s.push_back({std::string(l.n) + ".weight", {l.co, l.ci, l.k, l.k}});
-    s.push_back({std::string(l.n) + ".bias", {l.co}});
+    s.add(std::string(l.n) + ".weight", (int64_t)l.co * l.ci * l.k * l.k);
+    s.add(std::string(l.n) + ".bias", l.co);
   }
   return s;
 }
@@ -74,16 +52,16 @@ constexpr float kOpenBnEps = 1e-3f;  // superpoint_open.py:64
 
 // superpoint_open.py:91-112, registration order (lightglue_amd.sp_weights.superpoint_open_schema);
 // bn.num_batches_tracked (int64) is not part of the fp32 interface
-std::vector<Tensor> make_open_schema(int descriptor_dim) {
+lg::WeightSchema make_open_schema(int descriptor_dim) {
   const int ci[12] = {1, 64, 64, 64, 64, 128, 128, 128, 128, 256, 128, 256};
   const int co[12] = {64, 64, 64, 64, 128, 128, 128, 128, 256, 65, 256, descriptor_dim};
-  std::vector<Tensor> s;
+  lg::WeightSchema s;
   for (int i = 0; i < 12; ++i) {
     const std::string n = kOpenNames[i];
     const int k = (i == 9 || i == 11) ? 1 : 3;
-    s.push_back({n + ".conv.weight", {co[i], ci[i], k, k}});
-    s.push_back({n + ".conv.bias", {co[i]}});
-    for (const char* b : {"weight", "bias", "running_mean", "running_var"}) s.push_back({n + ".bn." + b, {co[i]}});
+    s.add(n + ".conv.weight", (int64_t)co[i] * ci[i] * k * k);
+    s.add(n + ".conv.bias", co[i]);
+    for (const char* b : {"weight", "bias", "running_mean", "running_var"}) s.add(n + ".bn." + b, co[i]);
   }
   return s;
 }
@@ -169,8 +147,7 @@ Work carve(char* base, const Shape& s, int Nh) {
 struct sp_handle {
   sp_config_t cfg;
   int device;
-  std::vector<Tensor> schema;
-  std::map<std::string, int> index;
+  lg::WeightSchema schema;
   std::vector<size_t> woff;  // fp32 offsets of the loaded tensors in wbuf
   float* wbuf = nullptr;
   float* gbuf = nullptr;     // repacked GEMM matrices + biases
@@ -187,19 +164,14 @@ struct sp_handle {
   bool have_last = false;
 };
 
-static int layer_index(const sp_handle* h, const std::string& name) {
-  auto it = h->index.find(name);
-  return it == h->index.end() ? -1 : it->second;
-}
-
 static int create_handle(const sp_config_t* cfg, int arch, int device, sp_handle_t** out) {
   if (cfg->descriptor_dim != 256) return fail(LG_E_INVALID, "descriptor_dim must be 256");
   if (cfg->nms_radius < 0 || cfg->nms_radius > 8) return fail(LG_E_INVALID, "nms_radius must be in [0, 8]");
   if (cfg->refinement_radius < 0 || cfg->remove_borders < 0) return fail(LG_E_INVALID, "negative radius / border");
   int n = 0;
-  SP_HIP(hipGetDeviceCount(&n));
+  LG_HIP(hipGetDeviceCount(&n));
   if (device < 0 || device >= n) return fail(LG_E_INVALID, "bad device");
-  SP_HIP(hipSetDevice(device));
+  LG_HIP(hipSetDevice(device));
   auto* h = new sp_handle();
   h->cfg = *cfg;
   h->device = device;
@@ -207,10 +179,9 @@ static int create_handle(const sp_config_t* cfg, int arch, int device, sp_handle
   h->sample_mode = arch == kArchOpen ? 2 : (cfg->legacy_sampling ? 1 : 0);
   h->schema = arch == kArchOpen ? make_open_schema(cfg->descriptor_dim) : make_schema(*cfg);
   size_t off = 0;
-  for (size_t i = 0; i < h->schema.size(); ++i) {
-    h->index[h->schema[i].name] = (int)i;
+  for (int i = 0; i < h->schema.size(); ++i) {
     h->woff.push_back(off);
-    off += (size_t)h->schema[i].numel();
+    off += (size_t)h->schema.numel(i);
   }
   hipError_t e = hipMalloc((void**)&h->wbuf, off * sizeof(float));
   if (e != hipSuccess) {
@@ -245,35 +216,23 @@ int sp_destroy(sp_handle_t* h) {
   return LG_OK;
 }
 
-int sp_weight_count(const sp_handle_t* h) { return h ? (int)h->schema.size() : 0; }
-const char* sp_weight_name(const sp_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].name.c_str() : nullptr;
-}
-int64_t sp_weight_numel(const sp_handle_t* h, int i) {
-  return (h && i >= 0 && i < (int)h->schema.size()) ? h->schema[i].numel() : -1;
-}
+int sp_weight_count(const sp_handle_t* h) { return h ? lg::weight_count(h->schema) : 0; }
+const char* sp_weight_name(const sp_handle_t* h, int i) { return h ? lg::weight_name(h->schema, i) : nullptr; }
+int64_t sp_weight_numel(const sp_handle_t* h, int i) { return h ? lg::weight_numel(h->schema, i) : -1; }
 
 int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float* const* tensors, const int64_t* numels,
                     void* stream) {
   if (!h || n < 0 || (n && (!names || !tensors || !numels))) return fail(LG_E_INVALID, "null argument");
-  SP_HIP(hipSetDevice(h->device));
+  LG_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int> seen(h->schema.size(), 0);
-  for (int i = 0; i < n; ++i) {
-    const int k = layer_index(h, names[i]);
-    if (k < 0) return fail(LG_E_WEIGHTS, std::string("unexpected key in state_dict: ") + names[i]);
-    if (seen[k]++) return fail(LG_E_WEIGHTS, std::string("duplicate key: ") + names[i]);
-    if (numels[i] != h->schema[k].numel())
-      return fail(LG_E_WEIGHTS, std::string("size mismatch for ") + names[i] + ": expected " +
-                                    std::to_string(h->schema[k].numel()) + " got " + std::to_string(numels[i]));
-  }
-  for (size_t k = 0; k < h->schema.size(); ++k)
-    if (!seen[k]) return fail(LG_E_WEIGHTS, "missing key in state_dict: " + h->schema[k].name);
-  for (int i = 0; i < n; ++i)
-    SP_HIP(hipMemcpyAsync(h->wbuf + h->woff[layer_index(h, names[i])], tensors[i], numels[i] * sizeof(float),
+  std::vector<int> src;
+  std::string err;
+  if (!h->schema.match(n, names, tensors, numels, src, err)) return fail(LG_E_WEIGHTS, err);
+  for (int k = 0; k < h->schema.size(); ++k)
+    LG_HIP(hipMemcpyAsync(h->wbuf + h->woff[k], tensors[src[k]], h->schema.numel(k) * sizeof(float),
                           hipMemcpyDeviceToDevice, st));
   const bool open = h->arch == kArchOpen;
-  auto T = [&](const std::string& nm) { return h->wbuf + h->woff[layer_index(h, nm)]; };
+  auto T = [&](const std::string& nm) { return h->wbuf + h->woff[h->schema.find(nm)]; };
   auto W = [&](int role) { return T(open ? std::string(kOpenNames[role]) + ".conv.weight" : std::string(kNonfreeNames[role]) + ".weight"); };
   auto Bi = [&](int role) { return T(open ? std::string(kOpenNames[role]) + ".conv.bias" : std::string(kNonfreeNames[role]) + ".bias"); };
   // open: the role's BatchNorm -> (s, t) [n] and stats (max |s|, max |t|, nullable)
@@ -314,26 +273,26 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   (void)hipFree(h->planes);
   h->gbuf = nullptr;
   h->planes = nullptr;
-  SP_HIP(hipMalloc((void**)&h->gbuf, off * sizeof(float)));
-  SP_HIP(hipMemsetAsync(h->gbuf, 0, off * sizeof(float), st));
+  LG_HIP(hipMalloc((void**)&h->gbuf, off * sizeof(float)));
+  LG_HIP(hipMemsetAsync(h->gbuf, 0, off * sizeof(float), st));
   float* G = h->gbuf;
   for (int i = 0; i < 7; ++i) {
-    SP_HIP(lg::sp_repack_conv(W(1 + i), enc_co[i], enc_ci[i], 3, G + h->enc[i].off, st));
-    SP_HIP(hipMemcpyAsync(G + h->enc[i].boff, Bi(1 + i), enc_co[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(lg::sp_repack_conv(W(1 + i), enc_co[i], enc_ci[i], 3, G + h->enc[i].off, st));
+    LG_HIP(hipMemcpyAsync(G + h->enc[i].boff, Bi(1 + i), enc_co[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   int hr = 0;
   if (det) {
-    SP_HIP(lg::sp_repack_conv(W(8), 256, 128, 3, G + h->heads.off, st));
-    SP_HIP(hipMemcpyAsync(G + h->heads.boff, Bi(8), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(lg::sp_repack_conv(W(8), 256, 128, 3, G + h->heads.off, st));
+    LG_HIP(hipMemcpyAsync(G + h->heads.boff, Bi(8), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
     hr = 256;
-    SP_HIP(hipMemcpyAsync(G + h->pb.off, W(9), 65 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->pb.boff, Bi(9), 65 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(G + h->pb.off, W(9), 65 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(G + h->pb.boff, Bi(9), 65 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   if (des) {
-    SP_HIP(lg::sp_repack_conv(W(10), 256, 128, 3, G + h->heads.off + (size_t)hr * 9 * 128, st));
-    SP_HIP(hipMemcpyAsync(G + h->heads.boff + hr, Bi(10), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->db.off, W(11), 256 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SP_HIP(hipMemcpyAsync(G + h->db.boff, Bi(11), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(lg::sp_repack_conv(W(10), 256, 128, 3, G + h->heads.off + (size_t)hr * 9 * 128, st));
+    LG_HIP(hipMemcpyAsync(G + h->heads.boff + hr, Bi(10), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(G + h->db.off, W(11), 256 * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LG_HIP(hipMemcpyAsync(G + h->db.boff, Bi(11), 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   std::vector<Mat*> mats;
   for (auto& m : h->enc) mats.push_back(&m);
@@ -345,31 +304,31 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
   // open: + (max |s|, max |t|) of conv1a, conv1b .. conv4b, detector.0, descriptor.0
   const int nf = (int)mats.size() * 3 + 2, na = open ? 20 : 0;
   float* dst = nullptr;
-  SP_HIP(hipMallocAsync((void**)&dst, (nf + na) * sizeof(float), st));
+  LG_HIP(hipMallocAsync((void**)&dst, (nf + na) * sizeof(float), st));
   if (open) {
-    SP_HIP(fold(0, 64, G + h->s1a, G + h->t1a, dst + nf));
-    for (int i = 0; i < 7; ++i) SP_HIP(fold(1 + i, enc_co[i], G + h->enc[i].soff, G + h->enc[i].toff, dst + nf + 2 + 2 * i));
-    SP_HIP(fold(8, 256, G + h->heads.soff, G + h->heads.toff, dst + nf + 16));
-    SP_HIP(fold(10, 256, G + h->heads.soff + 256, G + h->heads.toff + 256, dst + nf + 18));
+    LG_HIP(fold(0, 64, G + h->s1a, G + h->t1a, dst + nf));
+    for (int i = 0; i < 7; ++i) LG_HIP(fold(1 + i, enc_co[i], G + h->enc[i].soff, G + h->enc[i].toff, dst + nf + 2 + 2 * i));
+    LG_HIP(fold(8, 256, G + h->heads.soff, G + h->heads.toff, dst + nf + 16));
+    LG_HIP(fold(10, 256, G + h->heads.soff + 256, G + h->heads.toff + 256, dst + nf + 18));
     // the 1x1 heads have no ReLU: their BatchNorm folds into the weight rows and the bias before
     // the statistics and the fp16x3 split below (their own s / t slots hold the folded affine)
-    SP_HIP(fold(9, 65, G + h->pb.soff, G + h->pb.toff, nullptr));
-    SP_HIP(lg::sp_scale_rows(G + h->pb.off, G + h->pb.boff, G + h->pb.soff, G + h->pb.toff, 65, 256, st));
-    SP_HIP(fold(11, 256, G + h->db.soff, G + h->db.toff, nullptr));
-    SP_HIP(lg::sp_scale_rows(G + h->db.off, G + h->db.boff, G + h->db.soff, G + h->db.toff, 256, 256, st));
+    LG_HIP(fold(9, 65, G + h->pb.soff, G + h->pb.toff, nullptr));
+    LG_HIP(lg::sp_scale_rows(G + h->pb.off, G + h->pb.boff, G + h->pb.soff, G + h->pb.toff, 65, 256, st));
+    LG_HIP(fold(11, 256, G + h->db.soff, G + h->db.toff, nullptr));
+    LG_HIP(lg::sp_scale_rows(G + h->db.off, G + h->db.boff, G + h->db.soff, G + h->db.toff, 256, 256, st));
   }
   for (size_t i = 0; i < mats.size(); ++i) {
-    SP_HIP(lg::absmax(G + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
-    SP_HIP(lg::weight_range_stats(G + mats[i]->off, mats[i]->rows, mats[i]->K, G + mats[i]->boff, dst + 3 * i + 1, st));
+    LG_HIP(lg::absmax(G + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
+    LG_HIP(lg::weight_range_stats(G + mats[i]->off, mats[i]->rows, mats[i]->K, G + mats[i]->boff, dst + 3 * i + 1, st));
   }
-  SP_HIP(lg::weight_range_stats(W(0), 64, 9, Bi(0), dst + nf - 2, st));
+  LG_HIP(lg::weight_range_stats(W(0), 64, 9, Bi(0), dst + nf - 2, st));
   std::vector<float> hs(nf + na);
-  SP_HIP(hipMemcpyAsync(hs.data(), dst, (nf + na) * sizeof(float), hipMemcpyDeviceToHost, st));
-  SP_HIP(hipStreamSynchronize(st));
-  SP_HIP(hipFreeAsync(dst, st));
+  LG_HIP(hipMemcpyAsync(hs.data(), dst, (nf + na) * sizeof(float), hipMemcpyDeviceToHost, st));
+  LG_HIP(hipStreamSynchronize(st));
+  LG_HIP(hipFreeAsync(dst, st));
   size_t ptotal = 0;
   for (auto* m : mats) ptotal += 2 * (size_t)m->rows * m->K;
-  SP_HIP(hipMalloc((void**)&h->planes, ptotal * sizeof(_Float16)));
+  LG_HIP(hipMalloc((void**)&h->planes, ptotal * sizeof(_Float16)));
   size_t po = 0;
   for (size_t i = 0; i < mats.size(); ++i) {
     Mat& m = *mats[i];
@@ -379,7 +338,7 @@ int sp_load_weights(sp_handle_t* h, int n, const char* const* names, const float
       (void)std::frexp(hs[3 * i], &E);
       sw = std::min(std::max(4 - E, -100), 100);
     }
-    SP_HIP(lg::split_weight_h3(G + m.off, m.rows, m.K, std::ldexp(1.f, sw), h->planes + po, st));
+    LG_HIP(lg::split_weight_h3(G + m.off, m.rows, m.K, std::ldexp(1.f, sw), h->planes + po, st));
     m.poff = po;
     m.unscale = std::ldexp(1.f, -(11 + sw));
     m.g = hs[3 * i + 1];
@@ -437,25 +396,25 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
   const Work w = carve((char*)workspace, s, std::max(Nh, 256));
   if (!workspace || workspace_bytes < w.bytes)
     return fail(LG_E_WORKSPACE, "workspace too small: need " + std::to_string(w.bytes) + " bytes");
-  SP_HIP(hipSetDevice(h->device));
+  LG_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   const int B = s.B;
 
-  SP_HIP(hipMemsetAsync(w.rtab, 0, kSlots * lg::kRangeStride * sizeof(unsigned), st));
-  SP_HIP(lg::range_absmax(in->image, (size_t)B * s.C * s.H * s.W, w.rtab, 0, st));
+  LG_HIP(hipMemsetAsync(w.rtab, 0, kSlots * lg::kRangeStride * sizeof(unsigned), st));
+  LG_HIP(lg::range_absmax(in->image, (size_t)B * s.C * s.H * s.W, w.rtab, 0, st));
   auto ro = [&](int in_slot, float g, float add, int out_slot) {
     return lg::RangeOut{w.rtab, in_slot, -1, g, 0.f, add, out_slot, 1};
   };
   // gray weights sum to 1: |gray| <= max |image|
   const int rp1 = rows_pad_for(s.R1);
-  const float* W1a = h->wbuf + h->woff[layer_index(h, open ? "backbone.0.0.conv.weight" : "conv1a.weight")];
-  const float* B1a = h->wbuf + h->woff[layer_index(h, open ? "backbone.0.0.conv.bias" : "conv1a.bias")];
+  const float* W1a = h->wbuf + h->woff[h->schema.find(open ? "backbone.0.0.conv.weight" : "conv1a.weight")];
+  const float* B1a = h->wbuf + h->woff[h->schema.find(open ? "backbone.0.0.conv.bias" : "conv1a.bias")];
   // open: |relu(.) s + t| <= max|s| (g M + bmax) + max|t|
   if (open)
-    SP_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, h->gbuf + h->s1a, h->gbuf + h->t1a, w.bx, rp1,
+    LG_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, h->gbuf + h->s1a, h->gbuf + h->t1a, w.bx, rp1,
                          ro(0, h->smax1a * h->g1a, h->smax1a * h->b1a + h->tmax1a, 1), st));
   else
-    SP_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, nullptr, nullptr, w.bx, rp1, ro(0, h->g1a, h->b1a, 1), st));
+    LG_HIP(lg::sp_conv1a(in->image, B, s.C, s.H, s.W, W1a, B1a, nullptr, nullptr, w.bx, rp1, ro(0, h->g1a, h->b1a, 1), st));
 
   // encoder: (input image, its rows, K, spatial H x W, pool?) -> output
   struct Step { _Float16* x; _Float16* y; int H, W, Cin, Cout; bool pool; };
@@ -468,7 +427,7 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
     const int rpx = rows_pad_for(rin);
     const long long rout = t.pool ? (long long)B * (t.H / 2) * (t.W / 2) : rin;
     const int rpy = rows_pad_for(rout);
-    SP_HIP(lg::sp_zero_rows(t.x, (long long)rpx * t.Cin, rpx, t.Cin, (int)rin, st));
+    LG_HIP(lg::sp_zero_rows(t.x, (long long)rpx * t.Cin, rpx, t.Cin, (int)rin, st));
     lg::ConvH3Args a{};
     a.X = {t.x, (long long)rpx * t.Cin, rpx};
     a.B = B;
@@ -491,7 +450,7 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
       a.ro = ro(x_slot, m.smax * m.g, m.smax * m.bmax + m.tmax, y_slot);
     }
     a.pool = t.pool;
-    SP_HIP(lg::sp_conv3x3(a, st));
+    LG_HIP(lg::sp_conv3x3(a, st));
     return LG_OK;
   };
   for (int i = 0; i < 7; ++i)
@@ -518,34 +477,34 @@ int sp_forward(sp_handle_t* h, const sp_inputs_t* in, sp_outputs_t* out, void* w
     a.a1_slot = -1;
     a.ro = lg::range_none();
     a.ro_v = lg::range_none();
-    SP_HIP(lg::gemm_h3(a, lg::EPI_STORE, st));
+    LG_HIP(lg::gemm_h3(a, lg::EPI_STORE, st));
     return LG_OK;
   };
   float* scores = out->dense_scores ? out->dense_scores : w.scores;
   if (c.has_detector) {
     if (int r = head1x1(h->pb, 0, w.logits)) return r;
-    SP_HIP(lg::sp_detector_scores(w.logits, 256, B, s.Hc, s.Wc, scores, st));
+    LG_HIP(lg::sp_detector_scores(w.logits, 256, B, s.Hc, s.Wc, scores, st));
   }
   if (c.has_descriptor) {
     if (int r = head1x1(h->db, c.has_detector ? 8 : 0, w.desc)) return r;
-    SP_HIP(lg::sp_desc_normalize(w.desc, (int)s.Rc, w.desc, st));
+    LG_HIP(lg::sp_desc_normalize(w.desc, (int)s.Rc, w.desc, st));
     if (out->dense_descriptors)
-      SP_HIP(hipMemcpyAsync(out->dense_descriptors, w.desc, (size_t)s.Rc * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
+      LG_HIP(hipMemcpyAsync(out->dense_descriptors, w.desc, (size_t)s.Rc * 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   h->last = s;
   h->have_last = true;
   if (sparse) {
-    SP_HIP(lg::sp_nms(scores, B, s.Hs, s.Ws, c.nms_radius, w.mask, w.sup, w.ss, st));
-    SP_HIP(lg::sp_candidates(scores, w.mask, B, s.Hs, s.Ws, c.remove_borders, in->image_size, c.detection_threshold, w.key,
+    LG_HIP(lg::sp_nms(scores, B, s.Hs, s.Ws, c.nms_radius, w.mask, w.sup, w.ss, st));
+    LG_HIP(lg::sp_candidates(scores, w.mask, B, s.Hs, s.Ws, c.remove_borders, in->image_size, c.detection_threshold, w.key,
                              w.idx, w.blk, w.cnt, st));
     const int k = in->max_keypoints;
-    SP_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, s.Hs * s.Ws, k, w.sel, out->keypoint_scores, s.cap, out->counts, st));
-    SP_HIP(lg::sp_keypoints(w.sel, out->counts, B, s.cap, s.Hs, s.Ws, scores, c.refinement_radius, w.kp, st));
-    SP_HIP(lg::sp_sample(w.kp, out->counts, B, s.cap, w.desc, s.Hc, s.Wc, h->sample_mode, out->descriptors, out->keypoints,
+    LG_HIP(lg::sp_select(w.key, w.idx, w.cnt, B, s.Hs * s.Ws, k, w.sel, out->keypoint_scores, s.cap, out->counts, st));
+    LG_HIP(lg::sp_keypoints(w.sel, out->counts, B, s.cap, s.Hs, s.Ws, scores, c.refinement_radius, w.kp, st));
+    LG_HIP(lg::sp_sample(w.kp, out->counts, B, s.cap, w.desc, s.Hc, s.Wc, h->sample_mode, out->descriptors, out->keypoints,
                          st));
     if (out->host_counts) {
-      SP_HIP(hipMemcpyAsync(out->host_counts, out->counts, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SP_HIP(hipStreamSynchronize(st));
+      LG_HIP(hipMemcpyAsync(out->host_counts, out->counts, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      LG_HIP(hipStreamSynchronize(st));
     }
   }
   return LG_OK;
@@ -558,8 +517,8 @@ int sp_sample_descriptors(sp_handle_t* h, const float* keypoints, const int32_t*
   const int Nh = 256 * ((h->cfg.has_detector ? 1 : 0) + (h->cfg.has_descriptor ? 1 : 0));
   const Work w = carve((char*)workspace, h->last, std::max(Nh, 256));
   if (workspace_bytes < w.bytes) return fail(LG_E_WORKSPACE, "workspace too small");
-  SP_HIP(hipSetDevice(h->device));
-  SP_HIP(lg::sp_sample(keypoints, counts, B, capacity, w.desc, h->last.Hc, h->last.Wc, h->sample_mode, descriptors,
+  LG_HIP(hipSetDevice(h->device));
+  LG_HIP(lg::sp_sample(keypoints, counts, B, capacity, w.desc, h->last.Hc, h->last.Wc, h->sample_mode, descriptors,
                        nullptr, (hipStream_t)stream));
   return LG_OK;
 }

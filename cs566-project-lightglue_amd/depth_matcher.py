@@ -24,6 +24,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._native import _ptr
 from .pipeline import BaseModel
 
 
@@ -92,10 +93,6 @@ class Camera(_Rows):
         cx, cy = K[..., 0, 2], K[..., 1, 2]
         fx, fy = K[..., 0, 0], K[..., 1, 1]
         return cls(torch.stack([2 * cx, 2 * cy, fx, fy, cx, cy], -1))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _rows(x, B, dev, what):

@@ -20,11 +20,8 @@ import ctypes
 import torch
 
 from . import _lib
+from ._native import _ptr
 from .pipeline import BaseModel
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def gt_matches_from_homography(kp0, kp1, H, pos_th=3, neg_th=6, reward=True):

@@ -51,6 +51,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._native import NativeModule, _ptr
 from .weights import DEFAULT_CONF
 
 DATA_PATH = Path(__file__).resolve().parent.parent / "data"
@@ -129,10 +130,6 @@ class _TokenConfidence(nn.Module):  # lightglue.py:96-99
     def __init__(self, d):
         super().__init__()
         self.token = nn.Sequential(nn.Linear(d, 1), nn.Sigmoid())
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 # Extension keys (no reference counterpart).  "precision": matrix-core operand format of the HIP
@@ -423,7 +420,9 @@ class _LayerSlices(torch.autograd.Function):
         return out
 
 
-class LightGlue(nn.Module):
+class LightGlue(NativeModule):
+    _native_prefix = "lg"
+    _native_name = "lightglue_amd: parameter"
     default_conf = {**DEFAULT_CONF, **EXTENSION_CONF}
     required_data_keys = ["keypoints0", "keypoints1", "descriptors0", "descriptors1"]
     url = "https://github.com/cvg/LightGlue/releases/download/{}/{}_lightglue.pth"
@@ -450,9 +449,8 @@ class LightGlue(nn.Module):
         self.transformers = nn.ModuleList([_Layer(d) for _ in range(n)])
         self.log_assignment = nn.ModuleList([_MatchAssignment(d) for _ in range(n)])
         self.token_confidence = nn.ModuleList([_TokenConfidence(d) for _ in range(n - 1)])
-        self._handle = None
-        self._handle_device = None
-        self._weights_key = None
+        self._native_init()
+        self._cfg_key = None
         self._weight_entries = None
         self._weight_modules = None
         self._graphs = None  # compile(): {signature: (hipGraph, static inputs, static outputs, generation, workspace)}
@@ -460,7 +458,6 @@ class LightGlue(nn.Module):
         # free device memory a captured graph may point at, so graphs of older generations are
         # recaptured instead of replayed
         self._gen = 0
-        self._ws = None
 
         state_dict = None
         if conf.weights is not None:  # lightglue.py:402-421
@@ -547,52 +544,23 @@ class LightGlue(nn.Module):
             | (_lib.PREC_GEMM_F16 if bool(c.mp) else 0),
         )
 
-    def _ensure_handle(self, device, upload=True):
-        """The native handle for this config on ``device``; with ``upload`` the parameters are
-        (re)packed into it when they changed.  The training path passes raw parameter pointers
-        to every call and never needs the packed copy (upload=False)."""
-        lib = _lib.load()
+    def _config_key(self, cfg):
+        return tuple(getattr(cfg, f) for f, _ in _lib.LGConfig._fields_)
+
+    def _handle_stale(self, device):  # the config may be edited between forwards: the handle follows it
+        return self._handle_device != device or self._cfg_key != self._config_key(self._lib_config())
+
+    def _create_handle(self, lib, device, h):
         cfg = self._lib_config()
-        cfg_key = tuple(getattr(cfg, f) for f, _ in _lib.LGConfig._fields_)
-        if self._handle is not None and (self._handle_device != device or self._cfg_key != cfg_key):
-            lib.lg_destroy(self._handle)
-            self._handle = None
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            _lib.check(lib.lg_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "lg_create")
-            self._handle, self._handle_device, self._cfg_key = h, device, cfg_key
-            self._weights_key = None
-            self._gen += 1
-        if not upload:
-            return lib
-        key = self._weights_signature()
-        if key != self._weights_key:
-            sd = self.state_dict(keep_vars=True)
-            names = [n for n in sd]
-            ts = []
-            for n in names:
-                t = sd[n].detach()
-                if t.device != device or t.dtype != torch.float32:
-                    raise RuntimeError(
-                        f"lightglue_amd: parameter {n} is {t.dtype} on {t.device}; move the module to {device} in fp32"
-                    )
-                ts.append(t.contiguous())
-            arr_n = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
-            arr_p = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-            arr_k = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.lg_load_weights(self._handle, len(ts), arr_n, arr_p, arr_k, ctypes.c_void_p(stream)), "lg_load_weights")
-            torch.cuda.current_stream(device).synchronize()  # sources may be temporaries
-            self._weights_key = self._weights_signature()
-            self._gen += 1
-        return lib
+        _lib.check(lib.lg_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "lg_create")
+        self._cfg_key = self._config_key(cfg)
+
+    def _on_handle_event(self):  # a new handle or re-uploaded weights: see self._gen
+        self._gen += 1
 
     def reload_weights(self):
-        """Force the next forward to re-upload every parameter.  Needed only after writes the
-        forward cannot see: in-place writes through ``p.data`` (``p.data.copy_(...)``, EMA
-        updates) bump the version counter of a temporary tensor, not of ``p``.  Captured HIP graphs
-        (:meth:`compile`) are dropped as well."""
-        self._weights_key = None
+        """As the base's; captured HIP graphs (:meth:`compile`) are dropped as well."""
+        super().reload_weights()
         if self._graphs is not None:
             self._graphs = {}
 
@@ -627,15 +595,7 @@ class LightGlue(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):  # .to() / .cuda() / .float(): parameters may be new tensors
         self._weight_entries = None
-        self._weights_key = None
         return super()._apply(fn, *args, **kwargs)
-
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.lg_destroy(self._handle)
-        except Exception:
-            pass
 
     # ------------------------------------------------------------ forward
     def forward(self, data: dict) -> dict:
@@ -802,8 +762,7 @@ class LightGlue(nn.Module):
 
         ws_bytes = ctypes.c_size_t()
         _lib.check(lib.lg_workspace_bytes(self._handle, b, m, n, ctypes.byref(ws_bytes)), "lg_workspace_bytes")
-        if self._ws is None or self._ws.numel() < ws_bytes.value or self._ws.device != device:
-            self._ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=device)
+        ws = self._workspace_bytes(max(ws_bytes.value, 1), device)
         flags = _lib.LG_FWD_TRAINING_GATE if self.training else 0
         inp = _lib.LGInputs(b, m, n, *[_ptr(t) for t in (k0, k1, d0, d1, s0, s1, sc0, o0, sc1, o1)], flags,
                             _ptr(nk0), _ptr(nk1))
@@ -816,7 +775,7 @@ class LightGlue(nn.Module):
                              0, 0, 0, 0, _ptr(sim))
         stream = torch.cuda.current_stream(device).cuda_stream
         _lib.check(
-            lib.lg_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(self._ws), ws_bytes.value, ctypes.c_void_p(stream)),
+            lib.lg_forward(self._handle, ctypes.byref(inp), ctypes.byref(out), _ptr(ws), ws_bytes.value, ctypes.c_void_p(stream)),
             "lg_forward",
         )
         self.last_precision_used = _lib.PRECISION_NAMES[out.precision_used]

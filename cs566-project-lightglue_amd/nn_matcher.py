@@ -28,14 +28,11 @@ import ctypes
 import torch
 
 from . import _lib
+from ._native import _ptr
 from .lightglue import LightGlue
 from .pipeline import BaseModel
 
 LG_NN_RATIO, LG_NN_DISTANCE, LG_NN_MUTUAL = 1, 2, 4
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def nn_match(desc0, desc1, ratio_thresh=None, distance_thresh=None, mutual_check=True, similarity=True,

@@ -33,6 +33,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._native import _ptr
 from .lightglue import LightGlue, merge_conf
 
 INFO_FIELDS = ("success", "num_matches", "num_inliers", "best_t", "best_minimal_count", "rounds", "valid_hypotheses")
@@ -47,10 +48,6 @@ def __getattr__(name):
         globals()[name] = int(_lib.load().lg_ransac_lds_matches())
         return globals()[name]
     raise AttributeError(name)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _need(d, keys, what):

@@ -34,12 +34,9 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._native import NativeModule, _ptr
 from .lightglue import LightGlue, merge_conf
 from .sg_weights import SG_DEFAULT_CONF
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _mlp(channels):  # superglue.py:63-72 (parameter container)
@@ -81,7 +78,9 @@ class _AttentionalGNN(nn.Module):  # superglue.py:142-170
         self.names = list(layer_names)
 
 
-class SuperGlue(nn.Module):
+class SuperGlue(NativeModule):
+    _native_prefix = "sg"
+    _native_name = "lightglue_amd.SuperGlue: tensor"
     default_conf = SG_DEFAULT_CONF
     required_data_keys = ["view0", "view1", "keypoints0", "keypoints1", "descriptors0", "descriptors1",
                           "keypoint_scores0", "keypoint_scores1"]
@@ -101,10 +100,7 @@ class SuperGlue(nn.Module):
         self.gnn = _AttentionalGNN(conf.descriptor_dim, conf.GNN_layers)
         self.final_proj = nn.Conv1d(conf.descriptor_dim, conf.descriptor_dim, kernel_size=1, bias=True)
         self.register_parameter("bin_score", nn.Parameter(torch.tensor(1.0)))
-        self._handle = None
-        self._handle_device = None
-        self._weights_key = None
-        self._ws = None
+        self._native_init()
 
     # ------------------------------------------------------------ native handle
     def _lib_config(self):
@@ -126,59 +122,18 @@ class SuperGlue(nn.Module):
         return tuple((id(m), n, t.data_ptr(), t._version) for m in self.modules()
                      for n, t in list(m._parameters.items()) + list(m._buffers.items()) if t is not None)
 
-    def _ensure_handle(self, device, upload=True):
-        lib = _lib.load()
-        if self._handle is not None and self._handle_device != device:
-            lib.sg_destroy(self._handle)
-            self._handle = None
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            cfg = self._lib_config()
-            _lib.check(lib.sg_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sg_create")
-            self._handle, self._handle_device, self._weights_key = h, device, None
-        if not upload:
-            return lib
-        key = self._weights_signature()
-        if key != self._weights_key:
-            sd = {k: v for k, v in self.state_dict(keep_vars=True).items() if not k.endswith("num_batches_tracked")}
-            names = list(sd)
-            ts = []
-            for n in names:
-                t = sd[n].detach()
-                if t.device != device or t.dtype != torch.float32:
-                    raise RuntimeError(f"lightglue_amd.SuperGlue: tensor {n} is {t.dtype} on {t.device}; "
-                                       f"move the module to {device} in fp32")
-                ts.append(t.contiguous())
-            arr_n = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
-            arr_p = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-            arr_k = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.sg_load_weights(self._handle, len(ts), arr_n, arr_p, arr_k, ctypes.c_void_p(stream)),
-                       "sg_load_weights")
-            torch.cuda.current_stream(device).synchronize()
-            self._weights_key = key
-        return lib
+    def _create_handle(self, lib, device, h):
+        cfg = self._lib_config()
+        _lib.check(lib.sg_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sg_create")
 
-    def reload_weights(self):
-        self._weights_key = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self._weights_key = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.sg_destroy(self._handle)
-        except Exception:
-            pass
+    def _native_state(self):
+        # bn.num_batches_tracked is an int64 counter outside the fp32 interface
+        return {k: v for k, v in self.state_dict(keep_vars=True).items() if not k.endswith("num_batches_tracked")}
 
     def _workspace(self, lib, device, B, M, N):
         nb = ctypes.c_size_t()
         _lib.check(lib.sg_workspace_bytes(self._handle, B, M, N, ctypes.byref(nb)), "sg_workspace_bytes")
-        if self._ws is None or self._ws.numel() < nb.value or self._ws.device != device:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=device)
-        return self._ws, nb.value
+        return self._workspace_bytes(nb.value, device), nb.value
 
     # ------------------------------------------------------------ forward (superglue.py:253-307)
     def forward(self, data: dict, return_descriptors: bool = False) -> dict:

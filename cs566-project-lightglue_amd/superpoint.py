@@ -25,15 +25,14 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._native import NativeModule, _ptr
 from .lightglue import merge_conf
 from .sp_weights import SP_DEFAULT_CONF
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class SuperPoint(nn.Module):
+class SuperPoint(NativeModule):
+    _native_prefix = "sp"
+    _native_name = "lightglue_amd.SuperPoint: parameter"
     default_conf = SP_DEFAULT_CONF
     required_data_keys = ["image"]
     checkpoint_url = "https://github.com/magicleap/SuperGluePretrainedNetwork/raw/master/models/weights/superpoint_v1.pth"
@@ -63,10 +62,7 @@ class SuperPoint(nn.Module):
         if not conf.trainable:
             for p in self.parameters():
                 p.requires_grad = False
-        self._handle = None
-        self._handle_device = None
-        self._weights_key = None
-        self._ws = None
+        self._native_init()
 
     # ------------------------------------------------------------ native handle
     def _lib_config(self):
@@ -79,64 +75,14 @@ class SuperPoint(nn.Module):
         cfg = self._lib_config()
         _lib.check(lib.sp_create(ctypes.byref(cfg), device.index or 0, ctypes.byref(h)), "sp_create")
 
-    def _native_state(self):
-        """The tensors sp_load_weights takes, by schema name."""
-        return self.state_dict(keep_vars=True)
-
     def _weights_signature(self):
         return tuple((id(m), n, t.data_ptr(), t._version) for m in self.modules() for n, t in m._parameters.items()
                      if t is not None)
 
-    def _ensure_handle(self, device):
-        lib = _lib.load()
-        if self._handle is not None and self._handle_device != device:
-            lib.sp_destroy(self._handle)
-            self._handle = None
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            self._create_handle(lib, device, h)
-            self._handle, self._handle_device, self._weights_key = h, device, None
-        key = self._weights_signature()
-        if key != self._weights_key:
-            sd = self._native_state()
-            names = list(sd)
-            ts = []
-            for n in names:
-                t = sd[n].detach()
-                if t.device != device or t.dtype != torch.float32:
-                    raise RuntimeError(f"lightglue_amd.SuperPoint: parameter {n} is {t.dtype} on {t.device}; "
-                                       f"move the module to {device} in fp32")
-                ts.append(t.contiguous())
-            arr_n = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
-            arr_p = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-            arr_k = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.sp_load_weights(self._handle, len(ts), arr_n, arr_p, arr_k, ctypes.c_void_p(stream)),
-                       "sp_load_weights")
-            torch.cuda.current_stream(device).synchronize()
-            self._weights_key = key
-        return lib
-
-    def reload_weights(self):
-        self._weights_key = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self._weights_key = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.sp_destroy(self._handle)
-        except Exception:
-            pass
-
     def _workspace(self, lib, device, B, C, H, W, cap):
         nb = ctypes.c_size_t()
         _lib.check(lib.sp_workspace_bytes(self._handle, B, C, H, W, cap, ctypes.byref(nb)), "sp_workspace_bytes")
-        if self._ws is None or self._ws.numel() < nb.value or self._ws.device != device:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=device)
-        return self._ws, nb.value
+        return self._workspace_bytes(nb.value, device), nb.value
 
     # ------------------------------------------------------------ forward (superpoint.py:202-350)
     def forward(self, data: dict) -> dict:

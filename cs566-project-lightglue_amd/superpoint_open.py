@@ -33,10 +33,10 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._native import _ptr
 from .lightglue import merge_conf
 from .sp_weights import SPO_DEFAULT_CONF
 from .superpoint import SuperPoint as _NonfreeSuperPoint
-from .superpoint import _ptr
 
 
 class VGGBlock(nn.Sequential):  # superpoint_open.py:57-73
@@ -84,10 +84,7 @@ class SuperPoint(_NonfreeSuperPoint):
                 p.requires_grad = False
         # the modules that own tensors (the tree is fixed here): walked once, not per forward
         self._owners = [m for m in self.modules() if isinstance(m, (nn.Conv2d, nn.BatchNorm2d))]
-        self._handle = None
-        self._handle_device = None
-        self._weights_key = None
-        self._ws = None
+        self._native_init()
 
     # ------------------------------------------------------------ native handle
     def _create_handle(self, lib, device, h):

@@ -59,7 +59,8 @@ int sp_aliked_create(const sp_aliked_config_t* cfg, int device, sp_aliked_handle
 int sp_aliked_destroy(sp_aliked_handle_t* h);
 
 /* The reference's state_dict without the int64 bn.num_batches_tracked counters: fp32 device
- * tensors by name (block1..4, conv1..4, score_head.{0,2,4,6}, desc_head.*). */
+ * tensors by name (block1..4, conv1..4, score_head.{0,2,4,6}, desc_head.*).  The load is strict, as
+ * lg_load_weights: an unexpected, duplicate, wrongly sized or missing key is LG_E_WEIGHTS. */
 int sp_aliked_weight_count(const sp_aliked_handle_t* h);
 const char* sp_aliked_weight_name(const sp_aliked_handle_t* h, int index);
 int64_t sp_aliked_weight_numel(const sp_aliked_handle_t* h, int index);
