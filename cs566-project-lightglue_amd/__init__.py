@@ -28,6 +28,10 @@ def __getattr__(name):
         from .aliked import ALIKED
 
         return ALIKED
+    if name == "GlueStick":
+        from .gluestick import GlueStick
+
+        return GlueStick
     if name in ("SuperGlue", "NLLLoss"):
         from . import superglue
 

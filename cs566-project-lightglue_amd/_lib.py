@@ -110,6 +110,18 @@ EXPORTED_SYMBOLS = [
     "sp_aliked_deform_conv",
     "sp_aliked_set_profile",
     "sp_aliked_stage_ms",
+    # GlueStick point-and-line matcher (include/gluestick_mi355x.h; ABI 12, additive)
+    "sg_gluestick_create",
+    "sg_gluestick_destroy",
+    "sg_gluestick_weight_count",
+    "sg_gluestick_weight_name",
+    "sg_gluestick_weight_numel",
+    "sg_gluestick_load_weights",
+    "sg_gluestick_workspace_bytes",
+    "sg_gluestick_forward",
+    "sg_gluestick_line_update",
+    "sg_gluestick_double_softmax",
+    "sg_gluestick_line_scores",
     "sg_create",
     "sg_destroy",
     "sg_weight_count",
@@ -440,6 +452,67 @@ class SGOutputs(ctypes.Structure):  # sg_outputs_t
     ]
 
 
+SG_GLUESTICK_MAX_LINE_ITERS = 16
+
+
+class GSConfig(ctypes.Structure):  # sg_gluestick_config_t
+    _fields_ = [
+        ("descriptor_dim", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32),
+        ("layer_types", ctypes.c_int32 * SG_MAX_LAYERS),
+        ("n_kenc", ctypes.c_int32),
+        ("keypoint_encoder", ctypes.c_int32 * SG_MAX_KENC),
+        ("num_line_iterations", ctypes.c_int32),
+        ("filter_threshold", ctypes.c_float),
+    ]
+
+
+class GSInputs(ctypes.Structure):  # sg_gluestick_inputs_t
+    _fields_ = [
+        ("B", ctypes.c_int32),
+        ("M", ctypes.c_int32),
+        ("N", ctypes.c_int32),
+        ("L0", ctypes.c_int32),
+        ("L1", ctypes.c_int32),
+        ("keypoints0", _P),
+        ("keypoints1", _P),
+        ("descriptors0", _P),
+        ("descriptors1", _P),
+        ("scores0", _P),
+        ("scores1", _P),
+        ("image_size0", _P),
+        ("image_size1", _P),
+        ("image_w0", ctypes.c_int32),
+        ("image_h0", ctypes.c_int32),
+        ("image_w1", ctypes.c_int32),
+        ("image_h1", ctypes.c_int32),
+        ("lines0", _P),
+        ("lines1", _P),
+        ("lines_junc_idx0", _P),
+        ("lines_junc_idx1", _P),
+        ("line_scores0", _P),
+        ("line_scores1", _P),
+    ]
+
+
+class GSOutputs(ctypes.Structure):  # sg_gluestick_outputs_t
+    _fields_ = [
+        ("matches0", _P),
+        ("matches1", _P),
+        ("matching_scores0", _P),
+        ("matching_scores1", _P),
+        ("log_assignment", _P),
+        ("descriptors0", _P),
+        ("descriptors1", _P),
+        ("line_log_assignment", _P),
+        ("line_matches0", _P),
+        ("line_matches1", _P),
+        ("line_matching_scores0", _P),
+        ("line_matching_scores1", _P),
+        ("raw_line_scores", _P),
+    ]
+
+
 ASSIGN_ROUTES = {"materialised": 0, "recomputed": 1}  # LG_ASSIGN_*
 ASSIGN_SENTINEL_F, ASSIGN_SENTINEL_I = -123.456, -77  # LG_ASSIGN_SENTINEL_F (as fp32) / _I
 
@@ -626,6 +699,20 @@ def load():
         "sp_aliked_deform_conv": (ctypes.c_int, [_P, _P, _P, _P, i32, i32, i32, i32, i32, _P, _P, sz, _P]),
         "sp_aliked_set_profile": (ctypes.c_int, [_P, i32]),
         "sp_aliked_stage_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+        "sg_gluestick_create": (ctypes.c_int, [ctypes.POINTER(GSConfig), ctypes.c_int, ctypes.POINTER(_P)]),
+        "sg_gluestick_destroy": (ctypes.c_int, [_P]),
+        "sg_gluestick_weight_count": (ctypes.c_int, [_P]),
+        "sg_gluestick_weight_name": (ctypes.c_char_p, [_P, ctypes.c_int]),
+        "sg_gluestick_weight_numel": (ctypes.c_int64, [_P, ctypes.c_int]),
+        "sg_gluestick_load_weights": (
+            ctypes.c_int,
+            [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), _P],
+        ),
+        "sg_gluestick_workspace_bytes": (ctypes.c_int, [_P, i32, i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "sg_gluestick_forward": (ctypes.c_int, [_P, ctypes.POINTER(GSInputs), ctypes.POINTER(GSOutputs), _P, sz, _P]),
+        "sg_gluestick_line_update": (ctypes.c_int, [_P, i32, _P, _P, _P, i32, i32, i32, _P, _P]),
+        "sg_gluestick_double_softmax": (ctypes.c_int, [_P, ctypes.c_float, i32, i32, i32, _P, _P]),
+        "sg_gluestick_line_scores": (ctypes.c_int, [_P, _P, _P, _P, i32, i32, i32, i32, i32, _P, _P]),
         "sg_create": (ctypes.c_int, [ctypes.POINTER(SGConfig), ctypes.c_int, ctypes.POINTER(_P)]),
         "sg_destroy": (ctypes.c_int, [_P]),
         "sg_weight_count": (ctypes.c_int, [_P]),

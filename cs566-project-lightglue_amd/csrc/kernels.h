@@ -478,6 +478,8 @@ struct SgEncArgs {
   SgEncLayer layer[kSgMaxEnc];
   const int* cnt;       // [rows / n] or null: per-pair counts of a ragged batch -- padded points are
                         // neither read nor written
+  int endpoints;        // GlueStick's EndPtEncoder: kpts = line endpoints [rows][2] (n = 2L per image), scores
+                        // [rows / 2] line scores, ch[0] = 5 (x, y, offset to the other endpoint, score)
 };
 hipError_t sg_keypoint_encoder(const SgEncArgs& a, hipStream_t st);
 hipError_t sg_transpose(const float* src, int rows, int cols, float* dst, hipStream_t st);
@@ -594,5 +596,33 @@ size_t ransac_relpose_workspace_bytes(int B);
 hipError_t ransac_relpose(const RelposeCall& c, hipStream_t st);
 // the solver alone, one sample per thread: pts [S][5][4] normalised -> E [S][10][9], count [S]
 hipError_t essential_5pt(const float* pts, int S, double* E, int* count, hipStream_t st);
+
+// ---- GlueStick (gluefactory/models/matchers/gluestick.py, gluestick.hip) --------------------
+// Rows of the residual stream: image 0 of pair b at b*M, image 1 at B*M + b*N; endpoints likewise at
+// b*E0 and B*E0 + b*E1 (E = 2 L; endpoints e and e ^ 1 share a line).  N = E1 = 0: one image set.
+struct GsLayout {
+  int B, M, N, E0, E1;
+};
+// idx32[e] = idx64[e] clamped to [0, n): what the kernels index with (one image set per call)
+hipError_t gs_clamp_idx(const int64_t* idx64, size_t count, int n, int* idx32, hipStream_t st);
+// junction -> endpoint lists: deg[row], start[row] (offsets into list) and list[] = each junction's
+// endpoints in endpoint order (a stable fill: deterministic).  deg / start / cursor: B*(M+N) ints,
+// list: B*(E0+E1)
+hipError_t gs_build_csr(const int* idx32, const GsLayout& g, int* deg, int* start, int* cursor, int* list,
+                        hipStream_t st);
+// G[e] = [x[j(e)] | x[j(e ^ 1)] | enc[e]] (768 floats) for every endpoint e
+hipError_t gs_gather_endpoints(const float* X, const float* enc, const int* idx32, const GsLayout& g, float* G,
+                               hipStream_t st);
+// X[r] += mean over the junction's endpoints of U[e] (list order); rows without endpoints unchanged
+hipError_t gs_scatter_mean(float* X, int R, const float* U, const int* deg, const int* start, const int* list,
+                           hipStream_t st);
+// dst[b][e][0:256] = src[b][idx[b][e]][0:256] (src rows [B][n], row stride ld), idx clamped to [0, n)
+hipError_t gs_gather_rows256(const float* src, int ld, int n, const int64_t* idx, int B, int ne, float* dst,
+                             hipStream_t st);
+// log_double_softmax (gluestick.py:761-772): scores [B][M][N], bin -> out [B][M+1][N+1];
+// ws: 2 * B * (M + N) floats
+hipError_t gs_double_softmax(const float* scores, float bin, int B, int M, int N, float* out, float* ws, hipStream_t st);
+// raw[b][i][j] = 0.5 max(S[2i][2j] + S[2i+1][2j+1], S[2i][2j+1] + S[2i+1][2j]), S [B][2 L0][2 L1]
+hipError_t gs_line_combine(const float* S, int B, int L0, int L1, float* raw, hipStream_t st);
 
 }  // namespace lg

@@ -39,11 +39,31 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(SgEncArgs a) {
       const float scale = fmaxf(w, h) * 0.7f;
       v0 = (a.kpts[2 * (size_t)r] - w / 2.f) / scale;
       v1 = (a.kpts[2 * (size_t)r + 1] - h / 2.f) / scale;
-      v2 = a.scores ? a.scores[r] : 0.f;
+      // per-keypoint score; in endpoints mode the array holds one score per LINE (rows / 2
+      // entries) and is read below
+      if (a.scores && !a.endpoints) v2 = a.scores[r];
     }
     act[0][tid][0] = v0;
     act[0][tid][1] = v1;
     act[0][tid][2] = v2;
+    if (a.endpoints) {
+      // EndPtEncoder (gluestick.py:495-514): rows are line endpoints [B][2L][2], a.n = 2L; channels
+      // x, y, the offset to the line's other endpoint (row r ^ 1), and the line score, which the
+      // reference lays out as scores.repeat(1, 2): endpoint column c reads line c mod L
+      float o0 = 0.f, o1 = 0.f;
+      if (on) {
+        const int b = r / a.n, c = r - b * a.n, nl = a.n / 2;
+        const float w = a.size ? a.size[2 * b] : a.fw, h = a.size ? a.size[2 * b + 1] : a.fh;
+        const float scale = fmaxf(w, h) * 0.7f;
+        const size_t q = (size_t)(r ^ 1);
+        o0 = (a.kpts[2 * q] - w / 2.f) / scale - v0;
+        o1 = (a.kpts[2 * q + 1] - h / 2.f) / scale - v1;
+        v2 = a.scores[(size_t)b * nl + (c % nl)];
+      }
+      act[0][tid][2] = o0;
+      act[0][tid][3] = o1;
+      act[0][tid][4] = v2;
+    }
   }
   __syncthreads();
   int cur = 0;
@@ -88,9 +108,13 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(SgEncArgs a) {
 
 hipError_t sg_keypoint_encoder(const SgEncArgs& a, hipStream_t st) {
   if (a.rows <= 0) return hipSuccess;
-  if (a.nl < 1 || a.nl > kSgMaxEnc || a.ch[0] < 2 || a.ch[0] > 3 || a.n <= 0 || !a.out || a.ldo < a.ch[a.nl] ||
-      (a.desc && a.ch[a.nl] != kEncMaxC))
+  if (a.nl < 1 || a.nl > kSgMaxEnc || a.n <= 0 || !a.out || a.ldo < a.ch[a.nl]) return hipErrorInvalidValue;
+  if (a.desc && a.ch[a.nl] != kEncMaxC) return hipErrorInvalidValue;
+  if (a.endpoints) {  // x, y, offset, line score; endpoints come in pairs
+    if (a.ch[0] != 5 || !a.scores || a.n % 2 || a.rows % a.n) return hipErrorInvalidValue;
+  } else if (a.ch[0] < 2 || a.ch[0] > 3) {  // x, y (, keypoint score)
     return hipErrorInvalidValue;
+  }
   for (int l = 1; l <= a.nl; ++l)
     if (a.ch[l] <= 0 || a.ch[l] > kEncMaxC || a.ch[l] % 4) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sg_kenc_kernel, dim3((a.rows + kEncRows - 1) / kEncRows), dim3(256), 0, st, a);

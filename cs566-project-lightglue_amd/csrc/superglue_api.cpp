@@ -26,6 +26,7 @@
 #include "api_common.h"
 #include "common.h"
 #include "kernels.h"
+#include "sg_trunk.h"
 #include "train.h"
 
 namespace {
@@ -117,23 +118,6 @@ Work carve(char* base, int B, int M, int N) {
   return w;
 }
 
-// packed q/k/v row t*256 + h*64 + j <- proj.t row dim(j)*4 + h (dim(j): rotary-pair order of the
-// QKV epilogue, j < 32 -> 2j, else 2(j-32)+1); merge column h*64 + d <- d*4 + h
-std::vector<int> qkv_perm() {
-  std::vector<int> p(3 * D);
-  auto dim = [](int j) { return j < 32 ? 2 * j : 2 * (j - 32) + 1; };
-  for (int t = 0; t < 3; ++t)
-    for (int h = 0; h < H; ++h)
-      for (int j = 0; j < HD; ++j) p[t * D + h * HD + j] = t * D + dim(j) * H + h;
-  return p;
-}
-std::vector<int> merge_perm() {
-  std::vector<int> p(D);
-  for (int h = 0; h < H; ++h)
-    for (int d = 0; d < HD; ++d) p[h * HD + d] = d * H + h;
-  return p;
-}
-
 }  // namespace
 
 struct sg_handle {
@@ -147,19 +131,8 @@ struct sg_handle {
   float* buf = nullptr;      // packed / folded fp32 weights
   int* perm = nullptr;       // qkv_perm [768] | merge_perm [256]
   _Float16* planes = nullptr;
-  struct Mat {
-    size_t off, boff;   // floats into buf
-    int rows, K;
-    size_t poff;        // halfs into planes
-    float unscale;
-    float g, bmax;      // row-L1 max, |bias| max
-  };
-  struct Layer {
-    int type;
-    Mat qkv, w1, w2;    // qkv: 768 x 256 (stats: keys / values rows below)
-    float gK, bK, gV, bV;
-    size_t bn1;         // raw BatchNorm of mlp.1 (folded into w1)
-  };
+  using Mat = lg::SgMat;
+  using Layer = lg::SgLayer;
   std::vector<Layer> layers;
   Mat fin;
   struct Enc {
@@ -185,6 +158,187 @@ void sg_handle_grad_ready(const sg_handle* h, int layer, void* stream) {
   if (h->grad_hook) h->grad_hook(h->grad_hook_ctx, layer, stream);
 }
 const WeightSchema& sg_handle_schema(const sg_handle* h) { return h->schema; }
+
+// ---- the trunk shared with GlueStick (sg_trunk.h)
+#define SG_TRY(expr)                   \
+  do {                                 \
+    hipError_t _e = (expr);            \
+    if (_e != hipSuccess) return _e;   \
+  } while (0)
+
+// packed q/k/v row t*256 + h*64 + j <- proj.t row dim(j)*4 + h (dim(j): rotary-pair order of the
+// QKV epilogue, j < 32 -> 2j, else 2(j-32)+1); merge column h*64 + d <- d*4 + h
+std::vector<int> sg_layer_perm() {
+  std::vector<int> p(4 * D);
+  auto dim = [](int j) { return j < 32 ? 2 * j : 2 * (j - 32) + 1; };
+  for (int t = 0; t < 3; ++t)
+    for (int h = 0; h < H; ++h)
+      for (int j = 0; j < HD; ++j) p[t * D + h * HD + j] = t * D + dim(j) * H + h;
+  for (int h = 0; h < H; ++h)
+    for (int d = 0; d < HD; ++d) p[3 * D + h * HD + d] = d * H + h;
+  return p;
+}
+
+void sg_layer_layout(SgLayer& ly, int type, const std::function<size_t(size_t)>& take) {
+  ly.type = type;
+  ly.qkv = {take(3 * D * D), take(3 * D), 3 * D, D, 0, 0.f, 0.f, 0.f};
+  ly.w1 = {take(4 * D * D), take(2 * D), 2 * D, 2 * D, 0, 0.f, 0.f, 0.f};
+  ly.w2 = {take(2 * D * D), take(D), D, 2 * D, 0, 0.f, 0.f, 0.f};
+}
+
+hipError_t sg_pack_layer(const std::function<float*(const std::string&)>& raw, const std::string& p, SgLayer& ly,
+                         float* B, float* tmp, const int* perm, hipStream_t st) {
+  // q / k / v stacked [768][256] then gathered into the packed head-major order
+  float* stk = tmp;
+  float* stb = tmp + 3 * D * D;
+  for (int j = 0; j < 3; ++j) {
+    const std::string q = p + ".attn.proj." + std::to_string(j);
+    SG_TRY(hipMemcpyAsync(stk + (size_t)j * D * D, raw(q + ".weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SG_TRY(hipMemcpyAsync(stb + j * D, raw(q + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  SG_TRY(gather_rows(B + ly.qkv.off, stk, perm, 3 * D, D, st));
+  SG_TRY(gather_rows(B + ly.qkv.boff, stb, perm, 3 * D, 1, st));
+  // merge columns into context order, folded into mlp.0 (fold_out_proj: W1[:, 256:] Wm, b1 +=
+  // W1[:, 256:] bm), then the eval BatchNorm of mlp.1
+  float* wm = tmp + 3 * D * D + 3 * D + 512 * 256 + 512;
+  SG_TRY(sg_gather_cols(wm, raw(p + ".attn.merge.weight"), perm + 3 * D, D, D, st));
+  SG_TRY(hipMemcpyAsync(B + ly.w1.off, raw(p + ".mlp.0.weight"), 4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  SG_TRY(hipMemcpyAsync(B + ly.w1.boff, raw(p + ".mlp.0.bias"), 2 * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  SG_TRY(fold_out_proj(B + ly.w1.off, B + ly.w1.boff, wm, raw(p + ".attn.merge.bias"), tmp + 3 * D * D + 3 * D, st));
+  SG_TRY(sg_bn_fold(B + ly.w1.off, B + ly.w1.boff, raw(p + ".mlp.1.weight"), raw(p + ".mlp.1.bias"),
+                    raw(p + ".mlp.1.running_mean"), raw(p + ".mlp.1.running_var"), 2 * D, 2 * D, st));
+  SG_TRY(hipMemcpyAsync(B + ly.w2.off, raw(p + ".mlp.3.weight"), 2 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  SG_TRY(hipMemcpyAsync(B + ly.w2.boff, raw(p + ".mlp.3.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return hipSuccess;
+}
+
+hipError_t sg_finish_mats(float* B, const std::vector<SgMat*>& mats, std::vector<SgLayer>& layers,
+                          const std::vector<const float*>& scalars, std::vector<float>& scalars_out, _Float16** planes,
+                          hipStream_t st) {
+  const int L = (int)layers.size();
+  size_t total = 0;
+  for (auto* m : mats) total += 2 * (size_t)m->rows * m->K;
+  if (*planes) (void)hipFree(*planes);
+  *planes = nullptr;
+  SG_TRY(hipMalloc((void**)planes, total * sizeof(_Float16)));
+  const size_t nst = mats.size() * 3 + 4 * (size_t)L + scalars.size();
+  float* dst = nullptr;
+  SG_TRY(hipMallocAsync((void**)&dst, nst * sizeof(float), st));
+  for (size_t i = 0; i < mats.size(); ++i) {
+    SG_TRY(absmax(B + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
+    SG_TRY(weight_range_stats(B + mats[i]->off, mats[i]->rows, mats[i]->K, B + mats[i]->boff, dst + 3 * i + 1, st));
+  }
+  float* ls = dst + 3 * mats.size();
+  for (int i = 0; i < L; ++i) {
+    const auto& q = layers[i].qkv;
+    SG_TRY(weight_range_stats(B + q.off + (size_t)D * D, D, D, B + q.boff + D, ls + 4 * i, st));
+    SG_TRY(weight_range_stats(B + q.off + (size_t)2 * D * D, D, D, B + q.boff + 2 * D, ls + 4 * i + 2, st));
+  }
+  for (size_t k = 0; k < scalars.size(); ++k)
+    SG_TRY(hipMemcpyAsync(ls + 4 * L + k, scalars[k], sizeof(float), hipMemcpyDeviceToDevice, st));
+  std::vector<float> hs(nst);
+  SG_TRY(hipMemcpyAsync(hs.data(), dst, nst * sizeof(float), hipMemcpyDeviceToHost, st));
+  SG_TRY(hipStreamSynchronize(st));
+  SG_TRY(hipFreeAsync(dst, st));
+  size_t poff = 0;
+  for (size_t i = 0; i < mats.size(); ++i) {
+    SgMat& m = *mats[i];
+    int sw = 0;
+    const float mx = hs[3 * i];
+    if (mx > 0.f && std::isfinite(mx)) {
+      int E;
+      (void)std::frexp(mx, &E);
+      sw = std::min(std::max(4 - E, -100), 100);
+    }
+    SG_TRY(split_weight_h3(B + m.off, m.rows, m.K, std::ldexp(1.f, sw), *planes + poff, st));
+    m.poff = poff;
+    m.unscale = std::ldexp(1.f, -(11 + sw));
+    m.g = hs[3 * i + 1];
+    m.bmax = hs[3 * i + 2];
+    poff += 2 * (size_t)m.rows * m.K;
+  }
+  for (int i = 0; i < L; ++i) {
+    layers[i].gK = hs[3 * mats.size() + 4 * i];
+    layers[i].bK = hs[3 * mats.size() + 4 * i + 1];
+    layers[i].gV = hs[3 * mats.size() + 4 * i + 2];
+    layers[i].bV = hs[3 * mats.size() + 4 * i + 3];
+  }
+  scalars_out.assign(hs.begin() + 3 * mats.size() + 4 * L, hs.end());
+  return hipSuccess;
+}
+
+hipError_t sg_gnn_layer(const SgLayer& ly, const float* W, const _Float16* planes, const SgTrunkWork& w, int B, int M,
+                        int N, const RowMask& live, const int* c0, const int* c1, int s_x, int s_k, int s_v, int s_h,
+                        int s_xn, hipStream_t st) {
+  const int R = B * (M + N), RP = w.rows_pad;
+  unsigned* rt = w.rtab;
+  auto ro = [&](int in0, float g0, int in1, float g1, float add, int o, int track = 0) {
+    return RangeOut{rt, in0, in1, g0, g1, add, o, track, 0};
+  };
+  auto image = [&](_Float16* p, int K) { return PlaneRef{p, (long long)RP * K, RP}; };
+  auto wplanes = [&](GemmH3Args& g, const SgMat& m) {
+    g.W = {planes + m.poff, (long long)m.rows * m.K, m.rows};
+    g.acc_scale = m.unscale;
+    g.bias = W + m.boff;
+  };
+  const size_t img1 = (size_t)B * H * M * HD;
+  const long long ps = (long long)R * D;
+  {
+    HeadLayout hl;
+    memset(&hl, 0, sizeof(hl));
+    hl.B = B; hl.H = H; hl.M = M; hl.N = N; hl.cosb = nullptr; hl.sinb = nullptr;
+    hl.q = w.Q; hl.kp = w.KP; hl.vp = w.VP; hl.pstride = ps; hl.qk_scale = 1.f;
+    GemmH3Args g;
+    memset(&g, 0, sizeof(g));
+    g.out_scale = 1.f;
+    g.A0 = image(w.Xp, D); g.K0 = D; g.K = D; wplanes(g, ly.qkv);
+    g.rtab = rt; g.a0_slot = s_x; g.a1_slot = -1;
+    g.ro = ro(s_x, ly.gK, -1, 0.f, ly.bK, s_k, 1);
+    g.ro_v = ro(s_x, ly.gV, -1, 0.f, ly.bV, s_v, kRangeTrack | kRangeTwoSided);  // M[v] bounds the context (mlp.0's input)
+    g.R = R; g.Nout = 3 * D; g.hl = hl; g.rm = live;
+    SG_TRY(gemm_h3(g, EPI_QKV_ROT, st));
+  }
+  {
+    const void* kp1 = static_cast<const char*>(w.KP) + 2 * img1;
+    const void* vp1 = static_cast<const char*>(w.VP) + 2 * img1;
+    float* ctx1 = w.ctx + (size_t)B * M * D;
+    AttnSet a0, a1;
+    if (ly.type == 0) {  // self: layer(desc0, desc0), layer(desc1, desc1)
+      a0 = {w.Q, w.KP, w.VP, ps, w.ctx, M, M, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c0, nullptr};
+      a1 = {w.Q + img1, kp1, vp1, ps, ctx1, N, N, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c1, nullptr};
+    } else {  // cross: layer(desc0, desc1), layer(desc1, desc0)
+      a0 = {w.Q, kp1, vp1, ps, w.ctx, M, N, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c1, nullptr};
+      a1 = {w.Q + img1, w.KP, w.VP, ps, ctx1, N, M, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c0, nullptr};
+    }
+    SG_TRY(attention_f32(a0, a1, B, H, 0.125f, PREC_H3, st));  // 1 / sqrt(dim = 64) (:108)
+  }
+  // mlp.0 with merge and BatchNorm folded, ReLU -> hidden plane image (context planes carry the
+  // value planes' exponent, s_v)
+  {
+    GemmH3Args g;
+    memset(&g, 0, sizeof(g));
+    g.out_scale = 1.f;
+    g.A0 = image(w.Xp, D); g.K0 = D; g.A1 = image(w.Cp, D); g.K = 2 * D; wplanes(g, ly.w1);
+    g.rtab = rt; g.a0_slot = s_x; g.a1_slot = s_v;
+    g.R = R; g.Nout = 2 * D; g.relu = 1; g.rm = live;
+    g.Yp = w.Hp; g.yps = (long long)RP * 2 * D; g.yrows_pad = RP;
+    g.ro = ro(s_x, ly.w1.g, s_v, ly.w1.g, ly.w1.bmax, s_h, 1);
+    SG_TRY(gemm_h3(g, EPI_STORE, st));
+  }
+  {  // mlp.3 + residual: x = x + delta (fp32 rows and plane image)
+    GemmH3Args g;
+    memset(&g, 0, sizeof(g));
+    g.out_scale = 1.f;
+    g.A0 = image(w.Hp, 2 * D); g.K0 = 2 * D; g.K = 2 * D; wplanes(g, ly.w2);
+    g.rtab = rt; g.a0_slot = s_h; g.a1_slot = -1; g.rm = live;
+    g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
+    g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
+    g.ro = ro(s_x, 1.f, s_h, ly.w2.g, ly.w2.bmax, s_xn, 1);
+    SG_TRY(gemm_h3(g, EPI_STORE, st));
+  }
+  return hipSuccess;
+}
+#undef SG_TRY
 }  // namespace lg
 
 extern "C" {
@@ -261,11 +415,7 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
   }
   h->layers.assign(L, {});
   for (int i = 0; i < L; ++i) {
-    sg_handle::Layer& ly = h->layers[i];
-    ly.type = h->cfg.layer_types[i];
-    ly.qkv = {take(3 * D * D), take(3 * D), 3 * D, D, 0, 0.f, 0.f, 0.f};
-    ly.w1 = {take(4 * D * D), take(2 * D), 2 * D, 2 * D, 0, 0.f, 0.f, 0.f};
-    ly.w2 = {take(2 * D * D), take(D), D, 2 * D, 0, 0.f, 0.f, 0.f};
+    lg::sg_layer_layout(h->layers[i], h->cfg.layer_types[i], take);
   }
   h->fin = {take(D * D), take(D), D, D, 0, 0.f, 0.f, 0.f};
   const int kl = h->ch[h->ch.size() - 2];
@@ -276,11 +426,10 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
   LG_HIP(hipMalloc((void**)&h->buf, off * sizeof(float)));
   if (!h->perm) {
     LG_HIP(hipMalloc((void**)&h->perm, 4 * D * sizeof(int)));
-    std::vector<int> p = qkv_perm(), pm = merge_perm();
-    p.insert(p.end(), pm.begin(), pm.end());
+    const std::vector<int> p = lg::sg_layer_perm();
     LG_HIP(hipMemcpy(h->perm, p.data(), p.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  LG_HIP(hipMallocAsync((void**)&tmp, (3 * D * D + 3 * D + 512 * 256 + 512 + D * D) * sizeof(float), st));
+  LG_HIP(hipMallocAsync((void**)&tmp, lg::kSgTmpFloats * sizeof(float), st));
   float* B = h->buf;
   // keypoint encoder: transposed weights
   for (size_t l = 0; l < h->enc.size(); ++l) {
@@ -288,31 +437,8 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
     LG_HIP(lg::sg_transpose(raw(p + ".weight"), h->ch[l + 1], h->ch[l], B + h->enc[l].wt, st));
     LG_HIP(hipMemcpyAsync(B + h->enc[l].b, raw(p + ".bias"), h->ch[l + 1] * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  for (int i = 0; i < L; ++i) {
-    sg_handle::Layer& ly = h->layers[i];
-    const std::string p = "gnn.layers." + std::to_string(i);
-    // q / k / v stacked [768][256] then gathered into the packed head-major order
-    float* stk = tmp;
-    float* stb = tmp + 3 * D * D;
-    for (int j = 0; j < 3; ++j) {
-      const std::string q = p + ".attn.proj." + std::to_string(j);
-      LG_HIP(hipMemcpyAsync(stk + (size_t)j * D * D, raw(q + ".weight"), D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-      LG_HIP(hipMemcpyAsync(stb + j * D, raw(q + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    LG_HIP(lg::gather_rows(B + ly.qkv.off, stk, h->perm, 3 * D, D, st));
-    LG_HIP(lg::gather_rows(B + ly.qkv.boff, stb, h->perm, 3 * D, 1, st));
-    // merge columns into context order, folded into mlp.0 (fold_out_proj: W1[:, 256:] Wm, b1 +=
-    // W1[:, 256:] bm), then the eval BatchNorm of mlp.1
-    float* wm = tmp + 3 * D * D + 3 * D + 512 * 256 + 512;
-    LG_HIP(lg::sg_gather_cols(wm, raw(p + ".attn.merge.weight"), h->perm + 3 * D, D, D, st));
-    LG_HIP(hipMemcpyAsync(B + ly.w1.off, raw(p + ".mlp.0.weight"), 4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LG_HIP(hipMemcpyAsync(B + ly.w1.boff, raw(p + ".mlp.0.bias"), 2 * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LG_HIP(lg::fold_out_proj(B + ly.w1.off, B + ly.w1.boff, wm, raw(p + ".attn.merge.bias"), tmp + 3 * D * D + 3 * D, st));
-    LG_HIP(lg::sg_bn_fold(B + ly.w1.off, B + ly.w1.boff, raw(p + ".mlp.1.weight"), raw(p + ".mlp.1.bias"),
-                          raw(p + ".mlp.1.running_mean"), raw(p + ".mlp.1.running_var"), 2 * D, 2 * D, st));
-    LG_HIP(hipMemcpyAsync(B + ly.w2.off, raw(p + ".mlp.3.weight"), 2 * D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LG_HIP(hipMemcpyAsync(B + ly.w2.boff, raw(p + ".mlp.3.bias"), D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  }
+  for (int i = 0; i < L; ++i)
+    LG_HIP(lg::sg_pack_layer(raw, "gnn.layers." + std::to_string(i), h->layers[i], B, tmp, h->perm, st));
   if (h->enc_gemm) {
     const std::string p = "kenc.encoder." + std::to_string(3 * (h->ch.size() - 2));
     LG_HIP(hipMemcpyAsync(B + h->enc_last.off, raw(p + ".weight"), (size_t)D * kl * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -331,53 +457,9 @@ int sg_load_weights(sg_handle_t* h, int n, const char* const* names, const float
   }
   mats.push_back(&h->fin);
   if (h->enc_gemm) mats.push_back(&h->enc_last);
-  size_t total = 0;
-  for (auto* m : mats) total += 2 * (size_t)m->rows * m->K;
-  if (h->planes) (void)hipFree(h->planes);
-  h->planes = nullptr;
-  LG_HIP(hipMalloc((void**)&h->planes, total * sizeof(_Float16)));
-  const size_t nst = mats.size() * 3 + 4 * (size_t)L + 1;
-  float* dst = nullptr;
-  LG_HIP(hipMallocAsync((void**)&dst, nst * sizeof(float), st));
-  for (size_t i = 0; i < mats.size(); ++i) {
-    LG_HIP(lg::absmax(B + mats[i]->off, (size_t)mats[i]->rows * mats[i]->K, dst + 3 * i, st));
-    LG_HIP(lg::weight_range_stats(B + mats[i]->off, mats[i]->rows, mats[i]->K, B + mats[i]->boff, dst + 3 * i + 1, st));
-  }
-  float* ls = dst + 3 * mats.size();
-  for (int i = 0; i < L; ++i) {
-    const auto& q = h->layers[i].qkv;
-    LG_HIP(lg::weight_range_stats(B + q.off + (size_t)D * D, D, D, B + q.boff + D, ls + 4 * i, st));
-    LG_HIP(lg::weight_range_stats(B + q.off + (size_t)2 * D * D, D, D, B + q.boff + 2 * D, ls + 4 * i + 2, st));
-  }
-  LG_HIP(hipMemcpyAsync(ls + 4 * L, raw("bin_score"), sizeof(float), hipMemcpyDeviceToDevice, st));
-  std::vector<float> hs(nst);
-  LG_HIP(hipMemcpyAsync(hs.data(), dst, nst * sizeof(float), hipMemcpyDeviceToHost, st));
-  LG_HIP(hipStreamSynchronize(st));
-  LG_HIP(hipFreeAsync(dst, st));
-  size_t poff = 0;
-  for (size_t i = 0; i < mats.size(); ++i) {
-    sg_handle::Mat& m = *mats[i];
-    int sw = 0;
-    const float mx = hs[3 * i];
-    if (mx > 0.f && std::isfinite(mx)) {
-      int E;
-      (void)std::frexp(mx, &E);
-      sw = std::min(std::max(4 - E, -100), 100);
-    }
-    LG_HIP(lg::split_weight_h3(B + m.off, m.rows, m.K, std::ldexp(1.f, sw), h->planes + poff, st));
-    m.poff = poff;
-    m.unscale = std::ldexp(1.f, -(11 + sw));
-    m.g = hs[3 * i + 1];
-    m.bmax = hs[3 * i + 2];
-    poff += 2 * (size_t)m.rows * m.K;
-  }
-  for (int i = 0; i < L; ++i) {
-    h->layers[i].gK = hs[3 * mats.size() + 4 * i];
-    h->layers[i].bK = hs[3 * mats.size() + 4 * i + 1];
-    h->layers[i].gV = hs[3 * mats.size() + 4 * i + 2];
-    h->layers[i].bV = hs[3 * mats.size() + 4 * i + 3];
-  }
-  h->bin_score = hs[3 * mats.size() + 4 * L];
+  std::vector<float> scal;
+  LG_HIP(lg::sg_finish_mats(B, mats, h->layers, {raw("bin_score")}, scal, &h->planes, st));
+  h->bin_score = scal[0];
   LG_HIP(hipStreamSynchronize(st));
   h->loaded = true;
   return LG_OK;
@@ -517,65 +599,10 @@ static int forward_impl(sg_handle_t* h, const sg_inputs_t* in, const int32_t* n0
   }
 
   // ---- AttentionalGNN (superglue.py:148-170)
-  const size_t img1 = (size_t)B * H * M * HD;
-  const long long ps = (long long)R * D;
+  const SgTrunkWork tw{w.X, w.Q, w.ctx, w.KP, w.VP, w.Xp, w.Cp, w.Hp, rt, RP};
   for (int i = 0; i < h->cfg.n_layers; ++i) {
-    const sg_handle::Layer& ly = h->layers[i];
-    const int s_k = slot(), s_v = slot();
-    {
-      HeadLayout hl;
-      memset(&hl, 0, sizeof(hl));
-      hl.B = B; hl.H = H; hl.M = M; hl.N = N; hl.cosb = nullptr; hl.sinb = nullptr;
-      hl.q = w.Q; hl.kp = w.KP; hl.vp = w.VP; hl.pstride = ps; hl.qk_scale = 1.f;
-      GemmH3Args g;
-      memset(&g, 0, sizeof(g));
-      g.out_scale = 1.f;
-      g.A0 = image(w.Xp, D); g.K0 = D; g.K = D; wplanes(g, ly.qkv);
-      g.rtab = rt; g.a0_slot = s_x; g.a1_slot = -1;
-      g.ro = ro(s_x, ly.gK, -1, 0.f, ly.bK, s_k, 1);
-      g.ro_v = ro(s_x, ly.gV, -1, 0.f, ly.bV, s_v, kRangeTrack | kRangeTwoSided);  // M[v] bounds the context (mlp.0's input)
-      g.R = R; g.Nout = 3 * D; g.hl = hl; g.rm = live;
-      LG_HIP(gemm_h3(g, EPI_QKV_ROT, st));
-    }
-    {
-      const void* kp1 = static_cast<const char*>(w.KP) + 2 * img1;
-      const void* vp1 = static_cast<const char*>(w.VP) + 2 * img1;
-      float* ctx1 = w.ctx + (size_t)B * M * D;
-      AttnSet a0, a1;
-      if (ly.type == 0) {  // self: layer(desc0, desc0), layer(desc1, desc1)
-        a0 = {w.Q, w.KP, w.VP, ps, w.ctx, M, M, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c0, nullptr};
-        a1 = {w.Q + img1, kp1, vp1, ps, ctx1, N, N, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c1, nullptr};
-      } else {  // cross: layer(desc0, desc1), layer(desc1, desc0)
-        a0 = {w.Q, kp1, vp1, ps, w.ctx, M, N, w.Cp, (long long)RP * D, RP, 0, rt, s_k, c0, c1, nullptr};
-        a1 = {w.Q + img1, w.KP, w.VP, ps, ctx1, N, M, w.Cp, (long long)RP * D, RP, B * M, rt, s_k, c1, c0, nullptr};
-      }
-      LG_HIP(attention_f32(a0, a1, B, H, 0.125f, PREC_H3, st));  // 1 / sqrt(dim = 64) (:108)
-    }
-    // mlp.0 with merge and BatchNorm folded, ReLU -> hidden plane image (context planes carry the
-    // value planes' exponent, s_v)
-    const int s_h = slot(), s_xn = slot();
-    {
-      GemmH3Args g;
-      memset(&g, 0, sizeof(g));
-      g.out_scale = 1.f;
-      g.A0 = image(w.Xp, D); g.K0 = D; g.A1 = image(w.Cp, D); g.K = 2 * D; wplanes(g, ly.w1);
-      g.rtab = rt; g.a0_slot = s_x; g.a1_slot = s_v;
-      g.R = R; g.Nout = 2 * D; g.relu = 1; g.rm = live;
-      g.Yp = w.Hp; g.yps = (long long)RP * 2 * D; g.yrows_pad = RP;
-      g.ro = ro(s_x, ly.w1.g, s_v, ly.w1.g, ly.w1.bmax, s_h, 1);
-      LG_HIP(gemm_h3(g, EPI_STORE, st));
-    }
-    {  // mlp.3 + residual: x = x + delta (fp32 rows and plane image)
-      GemmH3Args g;
-      memset(&g, 0, sizeof(g));
-      g.out_scale = 1.f;
-      g.A0 = image(w.Hp, 2 * D); g.K0 = 2 * D; g.K = 2 * D; wplanes(g, ly.w2);
-      g.rtab = rt; g.a0_slot = s_h; g.a1_slot = -1; g.rm = live;
-      g.R = R; g.Nout = D; g.Y = w.X; g.ldy = D; g.res = w.X; g.ldr = D;
-      g.Yp = w.Xp; g.yps = (long long)RP * D; g.yrows_pad = RP;
-      g.ro = ro(s_x, 1.f, s_h, ly.w2.g, ly.w2.bmax, s_xn, 1);
-      LG_HIP(gemm_h3(g, EPI_STORE, st));
-    }
+    const int s_k = slot(), s_v = slot(), s_h = slot(), s_xn = slot();
+    LG_HIP(sg_gnn_layer(h->layers[i], W, h->planes, tw, B, M, N, live, c0, c1, s_x, s_k, s_v, s_h, s_xn, st));
     s_x = s_xn;
   }
   if (ragged) LG_HIP(zero_dead_rows(w.X, R, D, 0, live, st));  // padded rows leave as zeros, not stale workspace

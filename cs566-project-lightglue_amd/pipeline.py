@@ -10,7 +10,8 @@ model registry that resolve the matcher by name.
   pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
   the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
   the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`); ``"extractors.aliked"`` to ALIKED
-  (:mod:`~lightglue_amd.aliked`).  Other components (filters,
+  (:mod:`~lightglue_amd.aliked`); ``"matchers.gluestick"`` to the point-and-line matcher
+  (:mod:`~lightglue_amd.gluestick`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -202,7 +203,13 @@ def _aliked():
     return ALIKED
 
 
-_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _homography_matcher, _depth_matcher, _nn_matcher)
+def _gluestick():
+    from .gluestick import GlueStick
+
+    return GlueStick
+
+
+_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _depth_matcher, _nn_matcher)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -223,6 +230,9 @@ _REGISTRY = {
     # the SuperGlue matcher (gluefactory_nonfree/superglue.py), resolved lazily
     "gluefactory_nonfree.superglue": _superglue,
     "superglue": _superglue,
+    # the GlueStick point-and-line matcher (models/matchers/gluestick.py), resolved lazily
+    "matchers.gluestick": _gluestick,
+    "gluestick": _gluestick,
     # the homography ground truth (matchers/homography_matcher.py), resolved lazily
     "matchers.homography_matcher": _homography_matcher,
     "homography_matcher": _homography_matcher,
