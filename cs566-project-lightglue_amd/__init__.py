@@ -32,6 +32,10 @@ def __getattr__(name):
         from .gluestick import GlueStick
 
         return GlueStick
+    if name in ("WireframeExtractor", "LSD", "lines_to_wireframe", "sample_descriptors_corner_conv"):
+        from . import wireframe
+
+        return getattr(wireframe, name)
     if name in ("SuperGlue", "NLLLoss"):
         from . import superglue
 

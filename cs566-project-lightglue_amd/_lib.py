@@ -122,6 +122,11 @@ EXPORTED_SYMBOLS = [
     "sg_gluestick_line_update",
     "sg_gluestick_double_softmax",
     "sg_gluestick_line_scores",
+    # wireframe step in front of GlueStick (include/wireframe_mi355x.h; ABI 12, additive, no handle)
+    "lg_wireframe_workspace_bytes",
+    "lg_wireframe_forward",
+    "lg_wireframe_connectivity",
+    "lg_sample_descriptors_corner",
     "sg_create",
     "sg_destroy",
     "sg_weight_count",
@@ -513,6 +518,56 @@ class GSOutputs(ctypes.Structure):  # sg_gluestick_outputs_t
     ]
 
 
+LG_WIREFRAME_MAX_LINES, LG_WIREFRAME_MAX_DIM = 2048, 1024
+
+
+class WFConfig(ctypes.Structure):  # lg_wireframe_config_t
+    _fields_ = [
+        ("nms_radius", ctypes.c_double),
+        ("merge_points", ctypes.c_int32),
+        ("merge_line_endpoints", ctypes.c_int32),
+        ("force_num_keypoints", ctypes.c_int32),
+        ("force_num_lines", ctypes.c_int32),
+        ("s", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class WFInputs(ctypes.Structure):  # lg_wireframe_inputs_t
+    _fields_ = [
+        ("B", ctypes.c_int32),
+        ("L", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("J", ctypes.c_int32),
+        ("D", ctypes.c_int32),
+        ("Hc", ctypes.c_int32),
+        ("Wc", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("lines", _P),
+        ("line_scores", _P),
+        ("keypoints", _P),
+        ("keypoint_scores", _P),
+        ("descriptors", _P),
+        ("dense", _P),
+        ("fill_junctions", _P),
+        ("fill_keypoints", _P),
+    ]
+
+
+class WFOutputs(ctypes.Structure):  # lg_wireframe_outputs_t
+    _fields_ = [
+        ("points", _P),
+        ("scores", _P),
+        ("descriptors", _P),
+        ("lines", _P),
+        ("lines_junc_idx", _P),
+        ("counts", _P),
+        ("removed", _P),
+        ("connectivity", _P),
+        ("pl_associativity", _P),
+    ]
+
+
 ASSIGN_ROUTES = {"materialised": 0, "recomputed": 1}  # LG_ASSIGN_*
 ASSIGN_SENTINEL_F, ASSIGN_SENTINEL_I = -123.456, -77  # LG_ASSIGN_SENTINEL_F (as fp32) / _I
 
@@ -713,6 +768,13 @@ def load():
         "sg_gluestick_line_update": (ctypes.c_int, [_P, i32, _P, _P, _P, i32, i32, i32, _P, _P]),
         "sg_gluestick_double_softmax": (ctypes.c_int, [_P, ctypes.c_float, i32, i32, i32, _P, _P]),
         "sg_gluestick_line_scores": (ctypes.c_int, [_P, _P, _P, _P, i32, i32, i32, i32, i32, _P, _P]),
+        "lg_wireframe_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_wireframe_forward": (
+            ctypes.c_int,
+            [ctypes.POINTER(WFConfig), ctypes.POINTER(WFInputs), ctypes.POINTER(WFOutputs), _P, sz, _P],
+        ),
+        "lg_wireframe_connectivity": (ctypes.c_int, [_P, i32, i32, i32, i32, _P, _P]),
+        "lg_sample_descriptors_corner": (ctypes.c_int, [_P, _P, i32, i32, i32, i32, i32, i32, _P, _P]),
         "sg_create": (ctypes.c_int, [ctypes.POINTER(SGConfig), ctypes.c_int, ctypes.POINTER(_P)]),
         "sg_destroy": (ctypes.c_int, [_P]),
         "sg_weight_count": (ctypes.c_int, [_P]),

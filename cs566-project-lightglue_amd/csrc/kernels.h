@@ -625,4 +625,24 @@ hipError_t gs_double_softmax(const float* scores, float bin, int B, int M, int N
 // raw[b][i][j] = 0.5 max(S[2i][2j] + S[2i+1][2j+1], S[2i][2j+1] + S[2i+1][2j]), S [B][2 L0][2 L1]
 hipError_t gs_line_combine(const float* S, int B, int L0, int L1, float* raw, hipStream_t st);
 
+// ---- Wireframe step (gluefactory/models/lines/wireframe.py, wireframe.hip) ----
+// Rows of one image in points / scores / out_desc: J junction slots, then K keypoint slots.
+constexpr int kWfMaxEndpoints = 4096;  // endpoint coordinates and labels of one image live in LDS
+struct WfCall {
+  int B, L, K, J, D, Hc, Wc, s;
+  int merge_points, merge_endpoints, force_kp, force_lines;
+  double eps;  // nms_radius
+  const float *lines, *line_scores, *kp, *kp_scores, *kp_desc, *dense, *fill_junc, *fill_kp;
+  float *points, *scores, *out_desc, *new_lines;
+  int64_t* idx;            // [B][L][2]
+  int* counts;             // [2][B]
+  uint8_t *removed, *conn, *pl;  // nullable
+};
+size_t wireframe_workspace_bytes(int B, int L, int K);
+hipError_t wireframe_forward(const WfCall& c, void* workspace, hipStream_t st);
+hipError_t wireframe_connectivity(const int64_t* idx, int B, int L, int N, int identity_only, uint8_t* out,
+                                  hipStream_t st);
+hipError_t sample_descriptors_corner(const float* points, const float* dense, int B, int P, int Hc, int Wc, int D, int s,
+                                     float* out, hipStream_t st);
+
 }  // namespace lg

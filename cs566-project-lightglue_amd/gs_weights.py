@@ -222,3 +222,77 @@ def wireframe_pair(B, junc, pts, lines, seed=0, pad_junc=(0, 0), noise=0.05, wid
         a = np.stack(v)
         res[k] = a if a.dtype in (np.int64, np.bool_) else a.astype(np.float32)
     return res
+
+
+def wireframe_inputs(B, lines, keypoints, seed=0, max_num_lines=None, dim=256, nms_radius=3, width=160, height=120, s=8):
+    """Seeded inputs of the wireframe step (``lightglue_amd.wireframe``): per image ``lines[b]`` segments
+    (zero-padded to ``max_num_lines`` when given, ``valid_lines`` False there), ``keypoints`` points with
+    scores and unit descriptors, and a dense descriptor map [B, dim, height / s, width / s].
+
+    Endpoints sit in tight groups around well-separated sites (members < 0.8 r apart, sites > 1.7 r), so
+    many merge; a strip at the top holds a chain of four endpoints 0.9 r apart (one cluster wider than
+    2 r), two integer endpoints exactly r apart (they merge: ``<=``) and a keypoint exactly r from an
+    integer endpoint (it stays: ``<``).  About a quarter of the keypoints lie within 0.6 r of an
+    endpoint.  Every other endpoint-endpoint and keypoint-endpoint distance is outside +-1e-3 of r
+    (the draw repeats until it is); ``exact_pairs`` lists the deliberate ones as
+    (image, kind, index, endpoint index), kind 0 an endpoint pair and 1 a keypoint."""
+    r = float(nms_radius)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    K = int(keypoints)
+    Lcap = max(lines) if max_num_lines is None else int(max_num_lines)
+    assert max(lines) <= Lcap and min(lines) >= 4 and (max_num_lines is not None or len(set(lines)) == 1)
+    out = {k: [] for k in ("lines", "line_scores", "valid_lines", "keypoints", "keypoint_scores")}
+    exact = []
+    for b in range(B):
+        L = lines[b]
+        E = 2 * L
+        while True:
+            special = [(12 + 0.9 * r * i, 12.0) for i in range(4)] + [(60.0, 12.0), (60.0 + r, 12.0), (90.0, 12.0)]
+            n_rand = E - len(special)
+            n_sites = max(1, int(0.55 * n_rand))
+            sites = []
+            while len(sites) < n_sites:
+                c = rng.random(2) * np.array([width - 17, height - 48]) + np.array([8, 40])
+                if all(np.hypot(*(c - q)) >= 2.5 * r for q in sites):
+                    sites.append(c)
+            sites = np.asarray(sites)
+            which = np.concatenate([np.arange(n_sites), rng.integers(0, n_sites, n_rand - n_sites)])
+            ang, rad = rng.random(n_rand) * 2 * np.pi, rng.random(n_rand) * 0.4 * r
+            pts = sites[which] + np.stack([np.cos(ang), np.sin(ang)], 1) * rad[:, None]
+            ep = np.concatenate([np.asarray(special), pts]).astype(np.float32)
+            perm = rng.permutation(E)
+            ep = ep[perm]
+            where = np.argsort(perm)  # special point i is endpoint where[i]
+            kp = (rng.random((K, 2)) * np.array([width - 17, height - 17]) + 8).astype(np.float32)
+            near = rng.permutation(K)[: K // 4]
+            a2, r2 = rng.random(len(near)) * 2 * np.pi, rng.random(len(near)) * 0.6 * r
+            kp[near] = ep[rng.integers(0, E, len(near))] + (np.stack([np.cos(a2), np.sin(a2)], 1) * r2[:, None]).astype(np.float32)
+            kx = int(near[0]) if K else -1  # the keypoint exactly r from the integer endpoint (90, 12)
+            if K:
+                kp[kx] = (90.0 + 3.0, 12.0 + 4.0) if r == 5 else (90.0, 12.0 + r)
+            dee = np.hypot(*(ep[:, None].astype(np.float64) - ep[None].astype(np.float64)).transpose(2, 0, 1))
+            dke = np.hypot(*(kp[:, None].astype(np.float64) - ep[None].astype(np.float64)).transpose(2, 0, 1))
+            bee, bke = np.abs(dee - r) <= 1e-3, np.abs(dke - r) <= 1e-3
+            bee[where[4], where[5]] = bee[where[5], where[4]] = False
+            if K:
+                bke[kx, where[6]] = False
+            if not bee.any() and not bke.any() and dee[where[4], where[5]] == r and (not K or dke[kx, where[6]] == r):
+                break
+        exact.append((b, 0, int(where[4]), int(where[5])))
+        if K:
+            exact.append((b, 1, kx, int(where[6])))
+        ln = np.zeros((Lcap, 2, 2), np.float32)
+        ln[:L] = ep.reshape(L, 2, 2)
+        sc = np.zeros(Lcap, np.float32)
+        sc[:L] = (0.1 + 0.9 * rng.random(L)).astype(np.float32)
+        out["lines"].append(ln)
+        out["line_scores"].append(sc)
+        out["valid_lines"].append(np.arange(Lcap) < L)
+        out["keypoints"].append(kp)
+        out["keypoint_scores"].append(rng.random(K).astype(np.float32))
+    res = {k: np.stack(v) for k, v in out.items()}
+    d = rng.standard_normal((B, K, dim))
+    res["descriptors"] = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
+    res["dense_descriptors"] = rng.standard_normal((B, dim, height // s, width // s)).astype(np.float32)
+    res["exact_pairs"] = np.asarray(exact, np.int64).reshape(-1, 4)
+    return res

@@ -11,7 +11,8 @@ model registry that resolve the matcher by name.
   the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
   the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`); ``"extractors.aliked"`` to ALIKED
   (:mod:`~lightglue_amd.aliked`); ``"matchers.gluestick"`` to the point-and-line matcher
-  (:mod:`~lightglue_amd.gluestick`).  Other components (filters,
+  (:mod:`~lightglue_amd.gluestick`); ``"lines.wireframe"`` to the wireframe extractor in front of it and
+  ``"lines.lsd"`` to the LSD host wrapper (:mod:`~lightglue_amd.wireframe`).  Other components (filters,
   solvers) are supplied by the caller through :func:`register_model`.
 * :class:`LightGluePreTrainedMINE` — the reference's BaseModel wrapper
   (``matchers/lightglue_pretrained_MINE.py:8-36``): builds the matcher from its config and forwards
@@ -209,7 +210,20 @@ def _gluestick():
     return GlueStick
 
 
-_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _depth_matcher, _nn_matcher)
+def _wireframe():
+    from .wireframe import WireframeExtractor
+
+    return WireframeExtractor
+
+
+def _lsd():
+    from .wireframe import LSD
+
+    return LSD
+
+
+_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _depth_matcher, _nn_matcher,
+         _wireframe, _lsd)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -233,6 +247,13 @@ _REGISTRY = {
     # the GlueStick point-and-line matcher (models/matchers/gluestick.py), resolved lazily
     "matchers.gluestick": _gluestick,
     "gluestick": _gluestick,
+    # the wireframe extractor in front of GlueStick (models/lines/wireframe.py) and the LSD host
+    # wrapper (models/lines/lsd.py), resolved lazily
+    "lines.wireframe": _wireframe,
+    "wireframe": _wireframe,
+    "gluefactory.models.lines.wireframe": _wireframe,
+    "lines.lsd": _lsd,
+    "gluefactory.models.lines.lsd": _lsd,
     # the homography ground truth (matchers/homography_matcher.py), resolved lazily
     "matchers.homography_matcher": _homography_matcher,
     "homography_matcher": _homography_matcher,
@@ -252,11 +273,11 @@ def register_model(name, cls):
 
 def get_model(name):
     """models/__init__.py:7-30: the name as given, or with the ``matchers.`` / ``extractors.``
-    prefix the reference also tries (backward compatibility)."""
-    for path in (name, f"matchers.{name}", f"extractors.{name}"):
+    prefix the reference also tries (backward compatibility), or with ``lines.``."""
+    for path in (name, f"matchers.{name}", f"extractors.{name}", f"lines.{name}"):
         if path in _REGISTRY:
             obj = _REGISTRY[path]
             return obj() if obj in _LAZY else obj
     paths = [name, f"gluefactory.models.{name}", f"gluefactory.models.extractors.{name}",
-             f"gluefactory.models.matchers.{name}"]
+             f"gluefactory.models.matchers.{name}", f"gluefactory.models.lines.{name}"]
     raise RuntimeError(f'Model {name} not found in any of [{" ".join(paths)}]')
