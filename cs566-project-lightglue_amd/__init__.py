@@ -48,7 +48,8 @@ def __getattr__(name):
         from . import match_eval
 
         return getattr(match_eval, name)
-    if name in ("HomographyEstimator", "load_estimator", "eval_homography_robust", "ransac_homography"):
+    if name in ("HomographyEstimator", "PointLineHomographyEstimator", "load_estimator", "eval_homography_robust",
+                "ransac_homography", "ransac_homography_lines"):
         from . import robust
 
         return getattr(robust, name)

@@ -67,6 +67,9 @@ EXPORTED_SYMBOLS = [
     # batched robust homography estimation (ABI 12, no handle)
     "lg_ransac_lds_matches",
     "lg_ransac_homography",
+    # batched robust homography estimation from point and line matches (ABI 12, no handle)
+    "lg_ransac_lines_lds_capacity",
+    "lg_ransac_homography_lines",
     # batched robust relative pose and its five-point solver alone (ABI 12, no handle)
     "lg_ransac_relpose",
     "lg_essential_5pt",
@@ -681,6 +684,12 @@ def load():
         "lg_ransac_homography": (
             ctypes.c_int,
             [_P] * 3 + [i32] * 3 + [_P] * 3 + [i32, ctypes.c_double, ctypes.c_uint64, ctypes.c_double] + [_P] * 8,
+        ),
+        "lg_ransac_lines_lds_capacity": (ctypes.c_int, [_P, _P]),
+        "lg_ransac_homography_lines": (
+            ctypes.c_int,
+            [_P] * 3 + [i32] * 3 + [_P] * 5 + [i32] * 2 + [_P] * 3
+            + [i32, ctypes.c_double, ctypes.c_uint64, ctypes.c_double] + [_P] * 10,
         ),
         "lg_ransac_relpose": (
             ctypes.c_int,

@@ -572,6 +572,33 @@ struct RansacCall {
 };
 hipError_t ransac_homography(const RansacCall& c, hipStream_t st);
 
+// Batched hybrid LO-RANSAC for homographies from point and line matches (ransac_homography_lines.hip;
+// DESIGN.md §10p), one workgroup per pair.  Points as for RansacCall; either set may be empty.
+constexpr int RL_LDS_POINTS = 1024;  // point matches of a pair staged in LDS (fp64, normalised); more are read from m_kpts
+constexpr int RL_LDS_LINES = 448;    // line matches of a pair staged in LDS; more are read from m_lines
+struct RansacLinesCall {
+  const float *kp0, *kp1;    // [B][M][2], [B][N][2]
+  const int64_t* m0;         // [B][M], or null: slot i matches slot i
+  int B, M, N;
+  const int *num0, *num1;    // per-pair counts [B], or null
+  const float *ln0, *ln1;    // [B][L0][2][2], [B][L1][2][2]: endpoints (x, y)
+  const int64_t* lm0;        // [B][L0], or null: slot i matches slot i
+  int L0, L1;
+  const int *nl0, *nl1;      // per-pair line counts [B], or null
+  const float* th;           // [B] inlier thresholds in pixels
+  int max_iters;
+  double log_fail;           // log1p(-confidence)
+  uint64_t seed;
+  double min_len2;           // min_line_length squared, px^2
+  const float *H_gt, *size0;  // [B][9], [B][2], or null
+  float* H;                  // [B][9]
+  uint8_t *inliers, *line_inliers;  // [B][M], [B][L0]
+  int* info;                 // [B][12]
+  float *m_kpts, *m_lines;   // [B][M][4], [B][L0][8]
+  float* H_err;              // [B], or null
+};
+hipError_t ransac_homography_lines(const RansacLinesCall& c, hipStream_t st);
+
 // Batched five-point LO-RANSAC for the relative pose (ransac_relpose.hip), one
 // workgroup per pair; matches are selected and staged as for RansacCall.
 struct RelposeCall {

@@ -32,7 +32,7 @@ import torch
 from . import _lib
 from .depth_matcher import Pose, _rows
 from .lightglue import LightGlue, merge_conf
-from .robust import _NO_CPU, _PRED_KEYS, HomographyEstimator, _need, _ptr
+from .robust import _NO_CPU, _PRED_KEYS, HomographyEstimator, PointLineHomographyEstimator, _need, _ptr
 
 INFO_FIELDS = ("success", "num_matches", "num_inliers", "best_t", "best_minimal_count", "rounds", "valid_samples",
                "candidates_scored")
@@ -163,10 +163,13 @@ class RelativePoseEstimator:
 
 
 def load_estimator(type, estimator):
-    """``robust_estimators/__init__.py`` for both types this project has.  (``robust.load_estimator`` is
-    the homography-only one that the package exports.)"""
+    """``robust_estimators/__init__.py`` for both types this project has: ``"hip"`` for either, and
+    ``"homography_est"`` for the point-and-line homography estimator.  (``robust.load_estimator`` is the
+    homography-only one that the package exports.)"""
     if type not in ("relative_pose", "homography"):
         raise ValueError(f"relative_pose: unknown estimator type '{type}'")
+    if type == "homography" and estimator == "homography_est":
+        return PointLineHomographyEstimator
     if estimator != "hip":
         raise ValueError(f"relative_pose: unknown {type} estimator '{estimator}'; this project has 'hip'")
     return RelativePoseEstimator if type == "relative_pose" else HomographyEstimator

@@ -404,6 +404,58 @@ int lg_ransac_homography(const float* kpts0, const float* kpts1, const int64_t* 
                          const float* H_gt_or_null, const float* image_size0_or_null, float* H, uint8_t* inliers,
                          int32_t* info, float* m_kpts, float* H_error_or_null, void* stream);
 
+/* Batched robust homography estimation from point and line matches: a deterministic hybrid LO-RANSAC
+ *  in place of the reference's PointLineHomographyEstimator (robust_estimators/
+ * homography/homography_est.py), which eval_homography_robust uses for the superpoint+lsd+gluestick
+ * configs, for every pair of a batch in one launch.  Two more entries under ABI 12.  No handle, no
+ * workspace.
+ * Device inputs: the points and their counts are lg_ransac_homography's.  lines0 [B,L0,2,2], lines1
+ * [B,L1,2,2] fp32, 16-byte aligned: the endpoints (x, y) of every segment; line_matches0 [B,L0] int64,
+ * or null: L0 == L1 and slot i matches slot i.  num_lines0 / num_lines1 (nullable, together): device
+ * int32 [B].  Line i of pair b is live when i < num_lines0[b], 0 <= line_matches0[b,i] < num_lines1[b]
+ * and both segments are at least min_line_length px long.  Either set may be empty (M == 0 or
+ * L0 == 0; its pointers may then be null).  K = live points + live lines; feature i is point i below
+ * the number of live points, else a line.
+ * One similarity per image (mean to the origin, mean distance sqrt 2, over the live points and both
+ * endpoints of the live lines) is fixed for the whole run; the search runs in these coordinates with
+ * th_n = s1 * th.  An image-1 segment enters only as its line (a, b, c), a^2 + b^2 = 1, whatever the
+ * order of its endpoints; no endpoint correspondence is assumed.  Hypothesis t draws four features
+ * with lg_ransac_homography's sampler over K; two points with two lines is rejected (degenerate);
+ * the 8x9 system (two rows per point, one row per image-0 endpoint of a line) is reduced by
+ * Gauss-Jordan with complete pivoting, a pivot not above 1e-12 of the largest entry rejects the
+ * sample.  A point is an inlier by its forward transfer error, a line when both mapped image-0
+ * endpoints lie within the threshold of the image-1 line; a line counts once.  Rounds, the 8 local
+ * optimisation steps (unweighted DLT on the selected features in the fixed frame) and the stopping
+ * rule are lg_ransac_homography's over K.
+ * Device outputs: H [B,9] fp32 (h33 = 1); inliers [B,M], line_inliers [B,L0] uint8 in slot order, the
+ * classification in pixels of every live feature under the returned fp32 matrix (evaluated in fp64);
+ * info [B,12] int32: success, num_point_matches, num_line_matches, num_point_inliers,
+ * num_line_inliers, best_t, best_minimal_count, rounds, valid_hypotheses, 0, 0, 0; m_kpts [B,M,4] as
+ * lg_ransac_homography; m_lines [B,L0,8] fp32, 16-byte aligned: rows [0, num_line_matches) are the
+ * live lines (a0, b0, a1, b1) in slot order, the rest is not written; H_error [B] as
+ * lg_ransac_homography.  success is 0 with K < 4, no valid hypothesis, fewer than 4 final inliers in
+ * total or a vanishing h33; H is then the identity and both masks all zero.
+ * With L0 == 0 this is still the general solver without lg_ransac_homography's area test: the two
+ * entries agree in what they find, not bit for bit.
+ * All arithmetic is fp64; no atomics, identical results run to run.  Stream-ordered, asynchronous.
+ * LG_E_INVALID (checked before any device work): a null required pointer (ransac_th, H, info; the
+ * point arrays when M > 0, the line arrays when L0 > 0), a negative size, max_iters outside [1, 2^30],
+ * confidence outside (0, 1), a negative or non-finite min_line_length, one of a pair of counts alone,
+ * H_error without H_gt and image_size0, matches0 null with M != N, line_matches0 null with L0 != L1,
+ * a pointer off its natural alignment.
+ * B == 0 or M == L0 == 0: LG_OK, nothing launched, no output written.
+ * lg_ransac_lines_lds_capacity: the numbers of point and of line matches of a pair the kernel keeps in
+ * LDS; a set with more is read from m_kpts / m_lines in global memory (same results, slower). */
+int lg_ransac_lines_lds_capacity(int32_t* points, int32_t* lines);
+int lg_ransac_homography_lines(const float* kpts0, const float* kpts1, const int64_t* matches0_or_null, int32_t B,
+                               int32_t M, int32_t N, const int32_t* num0_or_null, const int32_t* num1_or_null,
+                               const float* lines0, const float* lines1, const int64_t* line_matches0_or_null, int32_t L0,
+                               int32_t L1, const int32_t* num_lines0_or_null, const int32_t* num_lines1_or_null,
+                               const float* ransac_th, int32_t max_iters, double confidence, uint64_t seed,
+                               double min_line_length, const float* H_gt_or_null, const float* image_size0_or_null,
+                               float* H, uint8_t* inliers, uint8_t* line_inliers, int32_t* info, float* m_kpts,
+                               float* m_lines, float* H_error_or_null, void* stream);
+
 /* Batched robust relative pose: a deterministic five-point LO-RANSAC in place of the
  * OpenCV / PoseLib / pycolmap estimators behind eval_relative_pose_robust (gluefactory/eval/utils.py:
  * 94-129), for every pair of a batch in one launch.  Two more entries under ABI 12.  No handle; the
