@@ -59,6 +59,14 @@ EXPORTED_SYMBOLS = [
     # pose-and-depth ground truth (ABI 12, no handle)
     "lg_gt_depth_workspace_bytes",
     "lg_gt_matches_from_pose_depth",
+    # line ground truth from a homography and the batched assignment solver (ABI 12, no handle)
+    "lg_gt_line_thresholds",
+    "lg_gt_line_counts_workspace_bytes",
+    "lg_gt_line_counts_homography",
+    "lg_gt_line_labels_workspace_bytes",
+    "lg_gt_line_labels",
+    "lg_linear_sum_assignment_workspace_bytes",
+    "lg_linear_sum_assignment",
     # nearest-neighbour matcher (ABI 12, no handle)
     "lg_nn_workspace_bytes",
     "lg_nn_match",
@@ -674,6 +682,17 @@ def load():
             [_P, _P, _P, i32, i32, _P, i32, i32, _P, _P, i32, _P, _P, i32, i32, i32] + [ctypes.c_double] * 4
             + [_P] * 15 + [sz, _P],
         ),
+        "lg_gt_line_thresholds": (
+            ctypes.c_int, [i32, ctypes.c_double, ctypes.c_double, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "lg_gt_line_counts_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_line_counts_homography": (
+            ctypes.c_int,
+            [_P, _P, _P] + [i32] * 8 + [ctypes.c_double, ctypes.c_double] + [_P] * 5 + [sz, _P],
+        ),
+        "lg_gt_line_labels_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_line_labels": (ctypes.c_int, [_P] * 6 + [i32] * 4 + [ctypes.c_double] + [_P] * 4 + [sz, _P]),
+        "lg_linear_sum_assignment_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_linear_sum_assignment": (ctypes.c_int, [_P, i32, i32, i32, _P, _P, _P, sz, _P]),
         "lg_nn_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_nn_match": (
             ctypes.c_int,

@@ -24,6 +24,30 @@ __device__ __forceinline__ float sqd(float ax, float ay, float bx, float by) {
   return dx * dx + dy * dy;
 }
 
+// from_homogeneous(points @ H^T, eps=1e-5) (geometry/homography.py:176-179, utils.py:30)
+__device__ __forceinline__ float2 warp(const float* h, float x, float y) {
+  const float u = (h[0] * x + h[1] * y) + h[2];
+  const float v = (h[3] * x + h[4] * y) + h[5];
+  const float w = ((h[6] * x + h[7] * y) + h[8]) + 1e-5f;
+  return make_float2(u / w, v / w);
+}
+
+// H^-1 as the adjugate over the determinant of the fp32 H in fp64, rounded once to fp32
+__device__ __forceinline__ void invert_h(const float* h, float* hi) {
+  const double a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7], i = h[8];
+  const double A = e * i - f * hh, Bc = -(d * i - f * g), C = d * hh - e * g;
+  const double inv = 1.0 / (a * A + bb * Bc + c * C);
+  hi[0] = (float)(A * inv);
+  hi[1] = (float)(-(bb * i - c * hh) * inv);
+  hi[2] = (float)((bb * f - c * e) * inv);
+  hi[3] = (float)(Bc * inv);
+  hi[4] = (float)((a * i - c * g) * inv);
+  hi[5] = (float)(-(a * f - c * d) * inv);
+  hi[6] = (float)(C * inv);
+  hi[7] = (float)(-(a * hh - bb * g) * inv);
+  hi[8] = (float)((a * e - bb * d) * inv);
+}
+
 inline size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
 
 // Zeros over n bytes: a scalar head up to the first 16-byte boundary, uint4 stores, a scalar tail.

@@ -51,14 +51,8 @@ __device__ __forceinline__ Dist pair_dist(float ax, float ay, float pax, float p
   return r;
 }
 
-// from_homogeneous(points @ H^T, eps=1e-5) (homography.py:176-179, utils.py:30)
-__device__ __forceinline__ float2 warp(const float* h, float x, float y) {
-  const float u = (h[0] * x + h[1] * y) + h[2];
-  const float v = (h[3] * x + h[4] * y) + h[5];
-  const float w = ((h[6] * x + h[7] * y) + h[8]) + 1e-5f;
-  return make_float2(u / w, v / w);
-}
-
+// warp and invert_h (the reference's from_homogeneous(points @ H^T) and the fp64-adjugate inverse) are in
+// gt_common.h, shared with the line ground truth (gt_lines.hip)
 __global__ __launch_bounds__(256) void gt_project(const float* __restrict__ kp0, const float* __restrict__ kp1,
                                                   const float* __restrict__ H, int M, int N, int bpp,
                                                   float* __restrict__ p01, float* __restrict__ p10) {
@@ -67,20 +61,7 @@ __global__ __launch_bounds__(256) void gt_project(const float* __restrict__ kp0,
   float h[9], hi[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) h[k] = H[(size_t)b * 9 + k];
-  {
-    const double a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7], i = h[8];
-    const double A = e * i - f * hh, Bc = -(d * i - f * g), C = d * hh - e * g;
-    const double inv = 1.0 / (a * A + bb * Bc + c * C);
-    hi[0] = (float)(A * inv);
-    hi[1] = (float)(-(bb * i - c * hh) * inv);
-    hi[2] = (float)((bb * f - c * e) * inv);
-    hi[3] = (float)(Bc * inv);
-    hi[4] = (float)((a * i - c * g) * inv);
-    hi[5] = (float)(-(a * f - c * d) * inv);
-    hi[6] = (float)(C * inv);
-    hi[7] = (float)(-(a * hh - bb * g) * inv);
-    hi[8] = (float)((a * e - bb * d) * inv);
-  }
+  invert_h(h, hi);
   if (t < M) {
     const size_t o = ((size_t)b * M + t) * 2;
     const float2 r = warp(h, kp0[o], kp0[o + 1]);

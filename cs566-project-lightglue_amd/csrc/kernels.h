@@ -519,6 +519,29 @@ struct GtDepthCall {
 size_t gt_depth_workspace_bytes(int B, int M, int N);
 hipError_t gt_matches_from_pose_depth(const GtDepthCall& c, void* workspace, hipStream_t st);
 
+// Line ground truth from a homography (gt_lines.hip; gt_generation.py:409-558).  Stage A: the two
+// [B,n0,n1] uint8 counts of close samples and the out-of-image flags; vis_min is the smallest count of
+// outside samples that makes a line "out" (gt_line_count_threshold_visibility).  Stage B: labels from
+// the counts; ov_min is the smallest count above npts * overlap_th (gt_line_count_threshold_overlap);
+// the fp64 cost lives in the workspace and the assignment is linear_sum_assignment's solver.
+int gt_line_count_threshold_visibility(int npts, double min_visibility_th);
+int gt_line_count_threshold_overlap(int npts, double overlap_th);
+size_t gt_line_counts_workspace_bytes(int B, int n0, int n1, int npts);
+hipError_t gt_line_counts_homography(const float* lines0, const float* lines1, const float* H, int B, int n0, int n1, int w0,
+                                     int h0, int w1, int h1, int npts, float dist_th, int vis_min, uint8_t* cnt0,
+                                     uint8_t* cnt1t, uint8_t* out_of0, uint8_t* out_of1, void* workspace, hipStream_t st);
+size_t gt_line_labels_workspace_bytes(int B, int n0, int n1);
+hipError_t gt_line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
+                          const uint8_t* valid0, const uint8_t* valid1, int B, int n0, int n1, int ov_min, uint8_t* positive,
+                          int64_t* m0, int64_t* m1, void* workspace, hipStream_t st);
+// SciPy's linear_sum_assignment (rectangular_lsap) per pair, one wave each: fp64 cost [B,nr,nc] ->
+// row_ind / col_ind [B, min(nr,nc)], SciPy's own result among the optimal ones; an infeasible pair
+// (no finite assignment) gets -1 everywhere.  The workspace is only needed when the state of a pair
+// does not fit 64 KiB of LDS.
+size_t linear_sum_assignment_workspace_bytes(int B, int nr, int nc);
+hipError_t linear_sum_assignment(const double* cost, int B, int nr, int nc, int64_t* row_ind, int64_t* col_ind,
+                                 void* workspace, hipStream_t st);
+
 // Nearest-neighbour matcher (nn_match.hip; matchers/nearest_neighbor_matcher.py:16-72).  r2 / d2: the
 // squared thresholds as the fp32 values the reference compares against; flags: 1 ratio test,
 // 2 distance test, 4 mutual check.  sim / la / num0 / num1 may be null (num0 and num1 together).

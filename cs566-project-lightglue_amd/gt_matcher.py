@@ -11,7 +11,9 @@ Differences from the reference:
 
 * ``reward`` (default True): ``False`` skips the reward (4 of the 5 bytes written per entry; neither
   LightGlue.loss nor SuperGlue.loss reads it) and omits the key.
-* ``use_lines: True`` raises at construction: line ground truth needs host-side Hungarian matching.
+* ``use_lines: True`` raises at construction under this name (its tests pin that).  Line ground truth from
+  homographies is ``matchers.line_homography_matcher`` (:mod:`~lightglue_amd.line_gt`): this matcher with
+  ``use_lines`` on, the assignment solved on the device.
 * With no keypoints in either image the reference returns a tuple its pipeline cannot merge; here the
   dict comes back with that tuple's contents (all-false assignment, matches -1) and empty / zero rest.
 """
@@ -91,7 +93,7 @@ class HomographyMatcher(BaseModel):
     def _init(self, conf):
         if conf.use_lines:
             raise NotImplementedError(
-                "homography_matcher: use_lines (line ground truth needs host-side Hungarian matching) is out of scope")
+                "homography_matcher: use_lines is not served under this name; use matchers.line_homography_matcher")
         if not conf.use_points:  # :26-27: the keypoints are required only with use_points
             self.required_data_keys = ["H_0to1"]
 

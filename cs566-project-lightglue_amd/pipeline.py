@@ -6,7 +6,8 @@ model registry that resolve the matcher by name.
   :class:`~lightglue_amd.lightglue.LightGlue` (the reference module's ``__main_model__``,
   ``lightglue.py:666``); ``"matchers.lightglue_pretrained_MINE"`` to the wrapper below;
   ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
-  HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.depth_matcher"`` to the
+  HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.line_homography_matcher"`` to
+  the same with line ground truth (:mod:`~lightglue_amd.line_gt`); ``"matchers.depth_matcher"`` to the
   pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
   the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
   the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`); ``"extractors.aliked"`` to ALIKED
@@ -186,6 +187,12 @@ def _homography_matcher():
     return HomographyMatcher
 
 
+def _line_homography_matcher():
+    from .line_gt import LineHomographyMatcher
+
+    return LineHomographyMatcher
+
+
 def _depth_matcher():
     from .depth_matcher import DepthMatcher
 
@@ -222,8 +229,8 @@ def _lsd():
     return LSD
 
 
-_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _depth_matcher, _nn_matcher,
-         _wireframe, _lsd)
+_LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _line_homography_matcher,
+         _depth_matcher, _nn_matcher, _wireframe, _lsd)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -257,6 +264,9 @@ _REGISTRY = {
     # the homography ground truth (matchers/homography_matcher.py), resolved lazily
     "matchers.homography_matcher": _homography_matcher,
     "homography_matcher": _homography_matcher,
+    # the same with line ground truth (use_lines, which the two names above refuse), resolved lazily
+    "matchers.line_homography_matcher": _line_homography_matcher,
+    "line_homography_matcher": _line_homography_matcher,
     # the pose-and-depth ground truth (matchers/depth_matcher.py), resolved lazily
     "matchers.depth_matcher": _depth_matcher,
     "depth_matcher": _depth_matcher,

@@ -310,6 +310,64 @@ int lg_gt_matches_from_pose_depth(const float* kp0, const float* kp1, const floa
                                   float* proj_1to0, uint8_t* visible0_u8, uint8_t* visible1_u8, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* Line ground truth from a homography: gt_line_matches_from_homography
+ * (gluefactory/geometry/gt_generation.py:409-558 with sample_pts, torch_perp_dist and
+ * warp_points_torch), what matchers.homography_matcher computes with use_lines.  Seven more entries
+ * under ABI 12.  No handle.  Two stages, each with its own workspace; running lg_gt_line_labels on the
+ * outputs of lg_gt_line_counts_homography gives the reference's (positive, m0, m1).
+ *
+ * Stage A, lg_gt_line_counts_homography.  Device inputs, fp32: lines0 [B,n0,4], lines1 [B,n1,4]
+ * (x1, y1, x2, y2), H [B,3,3]; h0, w0, h1, w1: the image sizes in pixels.  Endpoints are clamped to
+ * the image, npts samples per line are warped into the other image (H one way, H^-1 the other, formed
+ * as in lg_gt_matches_from_homography) and tested against every segment there with the reference's CPU
+ * fp32 arithmetic (segment length rounded to fp16, each product and sum rounded on its own; the
+ * reference's CUDA branch, which casts the operands to fp16, is not reproduced).  Device outputs, all
+ * uint8: num_close_pts0 [B,n0,n1] (samples of line j close to segment i of image 0), num_close_pts1_t
+ * [B,n0,n1] (samples of line i close to segment j of image 1), out_of0 [B,n1] (line j of image 1
+ * leaves image 0: mean(outside) >= 1 - min_visibility_th as the reference evaluates it in fp32),
+ * out_of1 [B,n0].  Nothing of size n0 * n1 * npts is kept: the workspace holds the warped samples
+ * (8 npts + 32 bytes per line).
+ *
+ * Stage B, lg_gt_line_labels.  Device inputs, uint8: the four outputs of stage A, valid_lines0 [B,n0],
+ * valid_lines1 [B,n1] (torch.bool bytes); overlap_th enters as count > npts * overlap_th evaluated as
+ * the reference does (fp32).  Device outputs: positive_u8 [B,n0,n1] 0/1, line_matches0 [B,n0] /
+ * line_matches1 [B,n1] int64 (-1 unmatched, -2 ignored).  The fp64 cost [B,n0,n1] lives in the
+ * workspace; the assignment is lg_linear_sum_assignment's solver.
+ *
+ * lg_gt_line_thresholds: the two integer thresholds the kernels compare counts with: the smallest
+ * count of outside samples that makes a line "out" and the smallest count above npts * overlap_th
+ * (npts + 1: no count qualifies).
+ *
+ * Stream-ordered, asynchronous, no atomics, identical results run to run.  LG_E_INVALID: a null
+ * pointer, a negative size, npts outside 2..255, n0 * n1 >= 2^31, a short or misaligned (16 bytes)
+ * workspace, a pointer off its natural alignment.  B, n0 or n1 == 0: LG_OK, nothing launched, no
+ * output written. */
+int lg_gt_line_thresholds(int32_t npts, double min_visibility_th, double overlap_th, int32_t* out_min_count,
+                          int32_t* close_min_count);
+int lg_gt_line_counts_workspace_bytes(int32_t B, int32_t n0, int32_t n1, int32_t npts, size_t* bytes);
+int lg_gt_line_counts_homography(const float* lines0, const float* lines1, const float* H, int32_t B, int32_t n0, int32_t n1,
+                                 int32_t h0, int32_t w0, int32_t h1, int32_t w1, int32_t npts, double dist_th,
+                                 double min_visibility_th, uint8_t* num_close_pts0, uint8_t* num_close_pts1_t,
+                                 uint8_t* out_of0, uint8_t* out_of1, void* workspace, size_t workspace_bytes, void* stream);
+int lg_gt_line_labels_workspace_bytes(int32_t B, int32_t n0, int32_t n1, size_t* bytes);
+int lg_gt_line_labels(const uint8_t* num_close_pts0, const uint8_t* num_close_pts1_t, const uint8_t* out_of0,
+                      const uint8_t* out_of1, const uint8_t* valid_lines0, const uint8_t* valid_lines1, int32_t B, int32_t n0,
+                      int32_t n1, int32_t npts, double overlap_th, uint8_t* positive_u8, int64_t* line_matches0,
+                      int64_t* line_matches1, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Batched linear sum assignment: SciPy's scipy.optimize.linear_sum_assignment (rectangular_lsap, the
+ * shortest-augmenting-path solver) for every pair of a batch, one wave per pair.  Device input: cost
+ * [B,nr,nc] fp64, finite.  Device outputs: row_ind, col_ind [B, min(nr,nc)] int64, row_ind ascending.
+ * The result is SciPy's own among the optimal ones: the same scan order, the same tie rule, the same
+ * fp64 reduced costs.  A pair without a finite assignment gets -1 in every slot (SciPy raises).  The
+ * workspace is needed (lg_linear_sum_assignment_workspace_bytes > 0) only when a pair's state,
+ * 28 bytes per column and 12 per row, exceeds 64 KiB of LDS.  Stream-ordered, asynchronous.
+ * LG_E_INVALID: a null pointer, a negative size, nr * nc >= 2^31, a short workspace, a pointer off
+ * 8 bytes.  B, nr or nc == 0: LG_OK, nothing launched. */
+int lg_linear_sum_assignment_workspace_bytes(int32_t B, int32_t nr, int32_t nc, size_t* bytes);
+int lg_linear_sum_assignment(const double* cost, int32_t B, int32_t nr, int32_t nc, int64_t* row_ind, int64_t* col_ind,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Nearest-neighbour matcher: what matchers.nearest_neighbor_matcher computes
  * (gluefactory/models/matchers/nearest_neighbor_matcher.py:16-72).  Two more entries under ABI 12.
  * No handle.  Device inputs, fp32: desc0 [B,M,D], desc1 [B,N,D], 1 <= D <= 512 (16-byte aligned
