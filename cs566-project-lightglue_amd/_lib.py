@@ -67,6 +67,12 @@ EXPORTED_SYMBOLS = [
     "lg_gt_line_labels",
     "lg_linear_sum_assignment_workspace_bytes",
     "lg_linear_sum_assignment",
+    # line ground truth from pose and depth (ABI 12, no handle)
+    "lg_gt_line_depth_thresholds",
+    "lg_gt_line_counts_pose_depth_workspace_bytes",
+    "lg_gt_line_counts_pose_depth",
+    "lg_gt_line_labels_visibility_workspace_bytes",
+    "lg_gt_line_labels_visibility",
     # nearest-neighbour matcher (ABI 12, no handle)
     "lg_nn_workspace_bytes",
     "lg_nn_match",
@@ -693,6 +699,18 @@ def load():
         "lg_gt_line_labels": (ctypes.c_int, [_P] * 6 + [i32] * 4 + [ctypes.c_double] + [_P] * 4 + [sz, _P]),
         "lg_linear_sum_assignment_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_linear_sum_assignment": (ctypes.c_int, [_P, i32, i32, i32, _P, _P, _P, sz, _P]),
+        "lg_gt_line_depth_thresholds": (
+            ctypes.c_int,
+            [i32, ctypes.c_double, ctypes.c_double, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "lg_gt_line_counts_pose_depth_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_line_counts_pose_depth": (
+            ctypes.c_int,
+            [_P, _P, _P, i32, i32, _P, i32, i32] + [i32] * 4 + [_P, _P, i32, _P, _P] + [i32] * 4
+            + [ctypes.c_double, ctypes.c_double] + [_P] * 9 + [sz, _P],
+        ),
+        "lg_gt_line_labels_visibility_workspace_bytes": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(sz)]),
+        "lg_gt_line_labels_visibility": (
+            ctypes.c_int, [_P] * 10 + [i32] * 4 + [ctypes.c_double] + [_P] * 4 + [sz, _P]),
         "lg_nn_workspace_bytes": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz)]),
         "lg_nn_match": (
             ctypes.c_int,

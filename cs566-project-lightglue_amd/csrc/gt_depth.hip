@@ -28,91 +28,13 @@
 #include <cstdint>
 
 #include "gt_common.h"
+#include "gt_depth_common.h"
 #include "kernels.h"
 
 namespace lg {
 namespace {
 
 using namespace gt;
-
-struct Cam {
-  float w, h, fx, fy, cx, cy, k1, k2, p1, p2;
-};
-__device__ __forceinline__ Cam load_cam(const float* r, int nd) {
-  Cam c = {r[0], r[1], r[2], r[3], r[4], r[5], 0.f, 0.f, 0.f, 0.f};
-  if (nd > 0) {
-    c.k1 = r[6];
-    c.k2 = r[7];
-  }
-  if (nd > 2) {
-    c.p1 = r[8];
-    c.p2 = r[9];
-  }
-  return c;
-}
-
-// depth.py:8-25.  The map value with <= 0 (and NaN) as NaN.  (cx, cy) are integral floats.
-__device__ __forceinline__ bool in_map(float cx, float cy, int H, int W) {
-  return cx >= 0.f && cy >= 0.f && cx <= (float)(W - 1) && cy <= (float)(H - 1);  // false for NaN
-}
-__device__ __forceinline__ float map_at(const float* depth, int W, float cx, float cy) {
-  const float v = depth[(size_t)(int)cy * W + (int)cx];
-  return v > 0.f ? v : __builtin_nanf("");
-}
-// grid_sample(align_corners=False, padding zeros): corners outside the map are skipped, a corner
-// inside is added even when its weight is 0 (a NaN neighbour makes the sum NaN), and a NaN sum
-// falls back to the nearest sample (round half to even; 0 outside the map).
-__device__ __forceinline__ float sample_depth(const float* depth, int H, int W, float x, float y) {
-  const float fw = (float)W, fh = (float)H;
-  const float ix = ((((x / fw) * 2.f - 1.f) + 1.f) * fw - 1.f) / 2.f;
-  const float iy = ((((y / fh) * 2.f - 1.f) + 1.f) * fh - 1.f) / 2.f;
-  const float x0 = floorf(ix), y0 = floorf(iy), x1 = x0 + 1.f, y1 = y0 + 1.f;
-  const float nw = (x1 - ix) * (y1 - iy), ne = (ix - x0) * (y1 - iy);
-  const float sw = (x1 - ix) * (iy - y0), se = (ix - x0) * (iy - y0);
-  float acc = 0.f;
-  if (in_map(x0, y0, H, W)) acc += map_at(depth, W, x0, y0) * nw;
-  if (in_map(x1, y0, H, W)) acc += map_at(depth, W, x1, y0) * ne;
-  if (in_map(x0, y1, H, W)) acc += map_at(depth, W, x0, y1) * sw;
-  if (in_map(x1, y1, H, W)) acc += map_at(depth, W, x1, y1) * se;
-  if (acc != acc) {
-    const float nx = rintf(ix), ny = rintf(iy);
-    acc = in_map(nx, ny, H, W) ? map_at(depth, W, nx, ny) : 0.f;
-  }
-  return acc;
-}
-
-struct P2 {
-  float x, y;
-  bool ok;
-};
-// Camera.cam2image (wrappers.py:337-385): project, distort (utils.py:90-127), denormalize, in_image
-__device__ __forceinline__ P2 cam2image(const Cam& c, int nd, float X, float Y, float Z) {
-  bool ok = Z > 1e-4f;
-  const float z = Z < 1e-4f ? 1e-4f : Z;  // clamp(min=eps); a NaN stays NaN
-  float x = X / z, y = Y / z;
-  if (nd > 0) {
-    const float r2 = x * x + y * y;
-    const float radial = c.k1 * r2 + c.k2 * (r2 * r2);
-    float ux = x + x * radial, uy = y + y * radial;
-    const float disc = 9.f * (c.k1 * c.k1) - 20.f * c.k2;
-    const bool limited = (c.k2 > 0.f && disc > 0.f) || (c.k2 <= 0.f && c.k1 > 0.f);
-    if (limited) {
-      const float limit = fabsf(c.k2 > 0.f ? (sqrtf(disc) - 3.f * c.k1) / (10.f * c.k2) : 1.f / (3.f * c.k1));
-      ok = ok && r2 < limit;
-    }
-    if (nd > 2) {
-      const float uv = x * y;
-      ux = (ux + (2.f * c.p1) * uv) + c.p2 * (r2 + 2.f * (x * x));
-      uy = (uy + (2.f * c.p2) * uv) + c.p1 * (r2 + 2.f * (y * y));
-    }
-    x = ux;
-    y = uy;
-  }
-  x = x * c.fx + c.cx;
-  y = y * c.fy + c.cy;
-  ok = ok && x >= 0.f && y >= 0.f && x <= c.w - 1.f && y <= c.h - 1.f;
-  return {x, y, ok};
-}
 
 // sym_epipolar_distance_all (epipolar.py:59-72) from the per-point halves: e0 = (F p0, sqrt(|F p0|_xy^2 + eps))
 // of the image-0 point, e1 = (p1, sqrt(|F^T p1|_xy^2 + eps)) of the image-1 point
@@ -143,12 +65,8 @@ __global__ __launch_bounds__(256) void gtd_points(PointArgs a, int bpp) {
   const Cam c0 = load_cam(a.cam0 + (size_t)b * cw, a.nd), c1 = load_cam(a.cam1 + (size_t)b * cw, a.nd);
   const Cam& ci = side ? c1 : c0;
   const Cam& cj = side ? c0 : c1;
-  const float* T = (side ? a.T10 : a.T01) + (size_t)b * 12;
-  float R[9], tr[3];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = T[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) tr[k] = T[9 + k];
+  const PoseRt T = load_pose((side ? a.T10 : a.T01) + (size_t)b * 12);
+  const float *R = T.R, *tr = T.t;
   const float* mi = side ? a.depth1 : a.depth0;
   const float* mj = side ? a.depth0 : a.depth1;
   const int Hi = side ? a.H1 : a.H0, Wi = side ? a.W1 : a.W0, Hj = side ? a.H0 : a.H1, Wj = side ? a.W0 : a.W1;
@@ -162,22 +80,17 @@ __global__ __launch_bounds__(256) void gtd_points(PointArgs a, int bpp) {
     valid = (side ? a.vin1 : a.vin0)[o] != 0;
   } else {
     d = sample_depth(mi + (size_t)b * Hi * Wi, Hi, Wi, kp.x, kp.y);
-    valid = d == d && d > 0.f;
+    valid = depth_valid(d);
     (side ? a.dk1 : a.dk0)[o] = d;
   }
   (side ? a.valid1 : a.valid0)[o] = valid;
 
   // depth.py:52-59: image2cam (no undistortion), times the depth, T.transform, cam2image
-  const float nx = (kp.x - ci.cx) / ci.fx, ny = (kp.y - ci.cy) / ci.fy;
-  const float X = nx * d, Y = ny * d, Z = 1.f * d;
-  const float qx = ((X * R[0] + Y * R[1]) + Z * R[2]) + tr[0];
-  const float qy = ((X * R[3] + Y * R[4]) + Z * R[5]) + tr[1];
-  const float qz = ((X * R[6] + Y * R[7]) + Z * R[8]) + tr[2];
-  const P2 pj = cam2image(cj, a.nd, qx, qy, qz);
+  const P2 pj = project_to(ci, cj, a.nd, T, kp.x, kp.y, d);
   bool vis = valid && pj.ok;
   if (a.cc) {  // depth.py:61-68, T_itoj.inv() as Pose.inv computes it (wrappers.py:173-177)
     const float dj = sample_depth(mj + (size_t)b * Hj * Wj, Hj, Wj, pj.x, pj.y);
-    const bool vdj = dj == dj && dj > 0.f;
+    const bool vdj = depth_valid(dj);
     const float lx = ((pj.x - cj.cx) / cj.fx) * dj, ly = ((pj.y - cj.cy) / cj.fy) * dj, lz = 1.f * dj;
     const float ti0 = -((R[0] * tr[0] + R[3] * tr[1]) + R[6] * tr[2]);
     const float ti1 = -((R[1] * tr[0] + R[4] * tr[1]) + R[7] * tr[2]);

@@ -24,6 +24,19 @@
 //                long for 64 KiB); also what lg_linear_sum_assignment runs
 //   gl_pairs     the ones of `positive` and the matched labels from the assignment
 //
+// The pose-and-depth variant, gt_line_matches_from_pose_depth (:207-406), shares everything but the
+// front end and the thresholds:
+//   gld_prepare  one wave per line of either image, the lanes over its samples: clamp to the depth map,
+//                the segment record, per sample the depth (sample_depth) and the projection into the
+//                other camera (gt_depth_common.h, the chain of gtd_points), the counts of visible
+//                samples, of samples with valid depth and of samples outside the other image by wave
+//                ballots, and the projected samples with NaN coordinates where a sample is not visible:
+//                close_pt is false for a NaN, so gl_counts runs unchanged and `close * visible` needs
+//                no second input
+//   gl_flags / gl_pairs<PerLineMin>  mask_close with a minimum count per row and per column, looked up
+//                from the line's visible count (:329-336), out_of only in unmatched0/1 (:341-342), and
+//                the depth-ignore flag or-ed into the ignored lines (:345-352)
+//
 // The "close" test follows the reference's CPU path in fp32.  Its CUDA branch casts the rotation and
 // the centred samples to fp16 "to reduce memory"; that is not reproduced (the fixtures come from the
 // CPU path).  This TU is built with -ffp-contract=off (Makefile): every product and sum is rounded on
@@ -35,6 +48,7 @@
 #include <cstdint>
 
 #include "gt_common.h"
+#include "gt_depth_common.h"
 #include "kernels.h"
 
 namespace lg {
@@ -98,6 +112,75 @@ __global__ __launch_bounds__(256) void gl_prepare(const float* __restrict__ line
   (second ? out_of0 : out_of1)[l] = nout >= vis_min;
 }
 
+struct LineDepthArgs {
+  const float *lines0, *lines1, *depth0, *depth1, *cam0, *cam1, *T01, *T10;
+  int B, n0, n1, H0, W0, H1, W1, ih0, iw0, ih1, iw1, nd, npts;
+  int out_min, valid_min;  // gt_line_count_threshold_visibility / _valid_depth
+  float *seg0, *seg1, *pts01, *pts10;
+  uint8_t *out_of0, *out_of1, *ignd0, *ignd1, *nvis0, *nvis1;
+};
+
+// One wave per line; lane k takes samples k, k + 64, ...: the four depth taps of neighbouring samples
+// fall in the same or adjacent cache lines, and a line's npts serial gather chains become
+// ceil(npts / 64).  The clamp is to the depth map (:250-260), the out-of-image test uses the image
+// size (:290-302) and runs on the projected coordinates before they are masked.
+__global__ __launch_bounds__(256) void gld_prepare(LineDepthArgs a) {
+  const size_t t = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  const size_t na = (size_t)a.B * a.n0, nb = (size_t)a.B * a.n1;
+  if (t >= na + nb) return;  // the whole wave
+  const bool second = t >= na;
+  const size_t l = second ? t - na : t;  // flat line index of its side
+  const size_t b = l / (second ? a.n1 : a.n0);
+  const float* ln = (second ? a.lines1 : a.lines0) + l * 4;
+  const int Hi = second ? a.H1 : a.H0, Wi = second ? a.W1 : a.W0;
+  const float wc = (float)(Wi - 1), hc = (float)(Hi - 1);
+  const float wo = (float)(second ? a.iw0 : a.iw1), ho = (float)(second ? a.ih0 : a.ih1);
+  const int cw = 6 + a.nd;
+  const Cam ci = load_cam((second ? a.cam1 : a.cam0) + b * cw, a.nd);  // the line's own camera
+  const Cam cj = load_cam((second ? a.cam0 : a.cam1) + b * cw, a.nd);  // the one it is projected into
+  const PoseRt T = load_pose((second ? a.T10 : a.T01) + b * 12);
+  const float* map = (second ? a.depth1 : a.depth0) + b * (size_t)Hi * Wi;
+
+  const float x1 = fminf(fmaxf(ln[0], 0.f), wc), y1 = fminf(fmaxf(ln[1], 0.f), hc);
+  const float x2 = fminf(fmaxf(ln[2], 0.f), wc), y2 = fminf(fmaxf(ln[3], 0.f), hc);
+  const float dx = x2 - x1, dy = y2 - y1;
+  if (lane == 0) {
+    const float size = __half2float(__float2half_rn(sqrtf(dx * dx + dy * dy)));
+    float* sg = (second ? a.seg1 : a.seg0) + l * 8;
+    *reinterpret_cast<float4*>(sg) = make_float4(x2, y2, dx / size, dy / size);
+    *reinterpret_cast<float4*>(sg + 4) = make_float4(size, 0.f, 0.f, 0.f);
+  }
+  const float den = (float)(a.npts - 1);
+  const float ddx = dx / den, ddy = dy / den;
+  float2* out = reinterpret_cast<float2*>(second ? a.pts10 : a.pts01) + l * (size_t)a.npts;
+  int nvis = 0, nvalid = 0, nout = 0;
+  for (int k0 = 0; k0 < a.npts; k0 += 64) {
+    const int k = k0 + lane;
+    bool vis = false, valid = false, outside = false;
+    if (k < a.npts) {
+      const float fk = (float)k;
+      const float px = x1 + ddx * fk, py = y1 + ddy * fk;
+      const float d = sample_depth(map, Hi, Wi, px, py);
+      valid = depth_valid(d);
+      const P2 q = project_to(ci, cj, a.nd, T, px, py, d);  // NaN without depth
+      vis = valid && q.ok;
+      outside = q.x < 0.f || q.y < 0.f || q.x >= wo || q.y >= ho;  // false for NaN, as :293-302
+      const float nan = __builtin_nanf("");
+      out[k] = vis ? make_float2(q.x, q.y) : make_float2(nan, nan);
+    }
+    nvis += __popcll(__ballot(vis));
+    nvalid += __popcll(__ballot(valid));
+    nout += __popcll(__ballot(outside));
+  }
+  if (lane == 0) {
+    // lines of image 1 leave image 0 (out_of0 [B, n1]) and the other way round
+    (second ? a.out_of0 : a.out_of1)[l] = nout >= a.out_min;
+    (second ? a.ignd1 : a.ignd0)[l] = nvalid < a.valid_min;
+    (second ? a.nvis1 : a.nvis0)[l] = (uint8_t)nvis;
+  }
+}
+
 // (perp_dist < dist_th) & overlaping of torch_perp_dist for one sample
 __device__ __forceinline__ int close_pt(float4 s, float size, float2 p, float dth) {
   const float cx = p.x - s.x, cy = p.y - s.y;
@@ -152,14 +235,42 @@ __global__ __launch_bounds__(kTile* kTile) void gl_counts(const float* __restric
 // ---------------------------------------------------------------------------------------------
 // Stage B
 
+// What differs between the two variants of stage B, as a policy of gl_flags and gl_pairs.
+// OneMin (homography, :491-500): one minimum count for every entry, out_of part of mask_close, only
+// invalid lines ignored.
+struct OneMin {
+  static constexpr bool kOutOfInMask = true;
+  int ov_min;
+  __device__ __forceinline__ int row_min(size_t) const { return ov_min; }
+  __device__ __forceinline__ int col_min(size_t) const { return ov_min; }
+  __device__ __forceinline__ bool ignored_row(size_t) const { return false; }
+  __device__ __forceinline__ bool ignored_col(size_t) const { return false; }
+};
+// PerLineMin (pose and depth, :329-352): cnt1t[i, j] against the minimum for the visible count of line
+// i, cnt0[i, j] against that of line j; out_of only in unmatched0/1; a line without enough valid depth
+// is ignored like an invalid one.  min_close[v] for v past npts is npts + 1: nothing passes.
+struct CloseTable {
+  uint16_t min_close[256];
+};
+struct PerLineMin {
+  static constexpr bool kOutOfInMask = false;
+  const uint8_t *nvis0, *nvis1, *ignd0, *ignd1;
+  CloseTable tab;
+  __device__ __forceinline__ int row_min(size_t row) const { return tab.min_close[nvis0[row]]; }
+  __device__ __forceinline__ int col_min(size_t col) const { return tab.min_close[nvis1[col]]; }
+  __device__ __forceinline__ bool ignored_row(size_t row) const { return ignd0[row] != 0; }
+  __device__ __forceinline__ bool ignored_col(size_t col) const { return ignd1[col] != 0; }
+};
+
 // Blocks [0, rb): one wave per row of a pair, the lanes stride its columns.  The rest: one thread per
-// column, walking the rows (adjacent threads read adjacent bytes).  mask_close (:491-496) is
-// cnt >= ov_min on both counts and neither line out of the image; unmatched = no mask_close entry, or
-// out of the image (:499-500); dead = unmatched | ~valid, what the cost and `positive` block.
+// column, walking the rows (adjacent threads read adjacent bytes).  mask_close is cnt1t >= the row's
+// minimum and cnt0 >= the column's (and, OneMin, neither line out of the image); unmatched = no
+// mask_close entry, or out of the image; dead = unmatched | ignored, what the cost and `positive` block.
+template <class Min>
 __global__ __launch_bounds__(256) void gl_flags(const uint8_t* __restrict__ cnt0, const uint8_t* __restrict__ cnt1t,
                                                 const uint8_t* __restrict__ out_of0, const uint8_t* __restrict__ out_of1,
                                                 const uint8_t* __restrict__ valid0, const uint8_t* __restrict__ valid1,
-                                                int B, int n0, int n1, int ov_min, unsigned rb,
+                                                int B, int n0, int n1, Min mn, unsigned rb,
                                                 uint8_t* __restrict__ dead0, uint8_t* __restrict__ dead1,
                                                 int64_t* __restrict__ m0, int64_t* __restrict__ m1) {
   if (blockIdx.x < rb) {
@@ -168,15 +279,16 @@ __global__ __launch_bounds__(256) void gl_flags(const uint8_t* __restrict__ cnt0
     const size_t b = row / n0;
     const int lane = threadIdx.x & 63;
     const bool out_i = out_of1[row] != 0;
+    const int min_i = mn.row_min(row);
     int any = 0;
-    if (!out_i)
+    if (!(Min::kOutOfInMask && out_i))
       for (int j = lane; j < n1; j += 64) {
-        const size_t o = row * n1 + j;
-        any |= (cnt0[o] >= ov_min && cnt1t[o] >= ov_min && !out_of0[b * n1 + j]) ? 1 : 0;
+        const size_t o = row * n1 + j, col = b * n1 + j;
+        any |= (cnt0[o] >= mn.col_min(col) && cnt1t[o] >= min_i && !(Min::kOutOfInMask && out_of0[col])) ? 1 : 0;
       }
     any = __any(any);
     if (lane == 0) {
-      const bool ign = valid0[row] == 0;
+      const bool ign = valid0[row] == 0 || mn.ignored_row(row);
       dead0[row] = (!any || out_i || ign) ? 1 : 0;
       m0[row] = ign ? -2 : -1;
     }
@@ -186,13 +298,14 @@ __global__ __launch_bounds__(256) void gl_flags(const uint8_t* __restrict__ cnt0
     const size_t b = col / n1;
     const int j = (int)(col - b * n1);
     const bool out_j = out_of0[col] != 0;
+    const int min_j = mn.col_min(col);
     int any = 0;
-    if (!out_j)
+    if (!(Min::kOutOfInMask && out_j))
       for (int i = 0; i < n0; ++i) {
-        const size_t o = (b * n0 + i) * n1 + j;
-        any |= (cnt0[o] >= ov_min && cnt1t[o] >= ov_min && !out_of1[b * n0 + i]) ? 1 : 0;
+        const size_t row = b * n0 + i, o = row * n1 + j;
+        any |= (cnt0[o] >= min_j && cnt1t[o] >= mn.row_min(row) && !(Min::kOutOfInMask && out_of1[row])) ? 1 : 0;
       }
-    const bool ign = valid1[col] == 0;
+    const bool ign = valid1[col] == 0 || mn.ignored_col(col);
     dead1[col] = (!any || out_j || ign) ? 1 : 0;
     m1[col] = ign ? -2 : -1;
   }
@@ -215,10 +328,11 @@ __global__ __launch_bounds__(256) void gl_cost(const uint8_t* __restrict__ cnt0,
   cost[tr ? (b * n1 + j) * n0 + i : t] = v;
 }
 
+template <class Min>
 __global__ __launch_bounds__(256) void gl_pairs(const uint8_t* __restrict__ cnt0, const uint8_t* __restrict__ cnt1t,
                                                 const uint8_t* __restrict__ dead0, const uint8_t* __restrict__ dead1,
                                                 const int64_t* __restrict__ row_ind, const int64_t* __restrict__ col_ind,
-                                                int B, int n0, int n1, int nmin, int ov_min,
+                                                int B, int n0, int n1, int nmin, Min mn,
                                                 uint8_t* __restrict__ positive, int64_t* __restrict__ m0,
                                                 int64_t* __restrict__ m1) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -229,7 +343,7 @@ __global__ __launch_bounds__(256) void gl_pairs(const uint8_t* __restrict__ cnt0
   const size_t o = (b * n0 + i) * n1 + j;
   // positive & mask_close with the unmatched / ignored rows and columns removed (:539-546); a row
   // without a positive stays -1, an ignored one -2 (:547-552), which gl_flags already wrote
-  if (cnt0[o] >= ov_min && cnt1t[o] >= ov_min && !dead0[b * n0 + i] && !dead1[b * n1 + j]) {
+  if (cnt0[o] >= mn.col_min(b * n1 + j) && cnt1t[o] >= mn.row_min(b * n0 + i) && !dead0[b * n0 + i] && !dead1[b * n1 + j]) {
     positive[o] = 1;
     m0[b * n0 + i] = j;
     m1[b * n1 + j] = i;
@@ -455,6 +569,26 @@ int gt_line_count_threshold_overlap(int npts, double overlap_th) {
   return npts + 1;
 }
 
+int gt_line_count_threshold_valid_depth(int npts, double min_visibility_th) {
+  // ignored: mean(valid) < min_visibility_th (:345-347), fp32 as above; the smallest count that is not
+  const float rhs = (float)min_visibility_th;
+  for (int c = 0; c <= npts; ++c)
+    if (!((float)c / (float)npts < rhs)) return c;
+  return npts + 1;
+}
+
+void gt_line_min_close_table(int npts, double overlap_th, int* min_close) {
+  // count > visible.float().sum(-1) * overlap_th (:329-336): the int64 count as fp32 against the fp32
+  // product of the fp32 sum and the Python float
+  const float th = (float)overlap_th;
+  for (int v = 0; v <= npts; ++v) {
+    const float rhs = (float)v * th;
+    int c = 0;
+    while (c <= npts && !((float)c > rhs)) ++c;
+    min_close[v] = c;  // npts + 1: no count qualifies
+  }
+}
+
 size_t gt_line_counts_workspace_bytes(int B, int n0, int n1, int npts) {
   const size_t l0 = (size_t)B * n0, l1 = (size_t)B * n1;
   return up256(l0 * 32) + up256(l1 * 32) + up256(l0 * npts * 8) + up256(l1 * npts * 8);
@@ -484,6 +618,33 @@ hipError_t gt_line_counts_homography(const float* lines0, const float* lines1, c
   return hipGetLastError();
 }
 
+hipError_t gt_line_counts_pose_depth(const GtLineDepthCall& c, void* workspace, hipStream_t st) {
+  char* w = static_cast<char*>(workspace);
+  const size_t l0 = (size_t)c.B * c.n0, l1 = (size_t)c.B * c.n1;
+  LineDepthArgs a;
+  a.lines0 = c.lines0, a.lines1 = c.lines1, a.depth0 = c.depth0, a.depth1 = c.depth1, a.cam0 = c.cam0, a.cam1 = c.cam1;
+  a.T01 = c.T_0to1, a.T10 = c.T_1to0;
+  a.B = c.B, a.n0 = c.n0, a.n1 = c.n1, a.H0 = c.H0, a.W0 = c.W0, a.H1 = c.H1, a.W1 = c.W1;
+  a.ih0 = c.ih0, a.iw0 = c.iw0, a.ih1 = c.ih1, a.iw1 = c.iw1, a.nd = c.n_dist, a.npts = c.npts;
+  a.out_min = c.out_min, a.valid_min = c.valid_min;
+  a.seg0 = reinterpret_cast<float*>(w);
+  w += up256(l0 * 32);
+  a.seg1 = reinterpret_cast<float*>(w);
+  w += up256(l1 * 32);
+  a.pts01 = reinterpret_cast<float*>(w);
+  w += up256(l0 * c.npts * 8);
+  a.pts10 = reinterpret_cast<float*>(w);
+  a.out_of0 = c.out_of0, a.out_of1 = c.out_of1, a.ignd0 = c.ignore_depth0, a.ignd1 = c.ignore_depth1;
+  a.nvis0 = c.num_visible0, a.nvis1 = c.num_visible1;
+  gld_prepare<<<dim3((unsigned)((l0 + l1 + 3) / 4)), dim3(256), 0, st>>>(a);
+  const int ti_n = (c.n0 + kTile - 1) / kTile, tj_n = (c.n1 + kTile - 1) / kTile;
+  const int stride = c.npts | 1;
+  const size_t lds = (size_t)2 * kTile * stride * sizeof(float2);
+  gl_counts<<<dim3((unsigned)((size_t)c.B * ti_n * tj_n)), dim3(kTile * kTile), lds, st>>>(
+      a.seg0, a.seg1, a.pts01, a.pts10, c.n0, c.n1, ti_n, tj_n, c.npts, stride, c.dist_th, c.cnt0, c.cnt1t);
+  return hipGetLastError();
+}
+
 size_t linear_sum_assignment_workspace_bytes(int B, int nr, int nc) {
   return lsa_global_state_bytes(B, imin(nr, nc), imax(nr, nc));
 }
@@ -500,9 +661,11 @@ size_t gt_line_labels_workspace_bytes(int B, int n0, int n1) {
          lsa_global_state_bytes(B, nmin, nmax);
 }
 
-hipError_t gt_line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
-                          const uint8_t* valid0, const uint8_t* valid1, int B, int n0, int n1, int ov_min, uint8_t* positive,
-                          int64_t* m0, int64_t* m1, void* workspace, hipStream_t st) {
+namespace {
+template <class Min>
+hipError_t line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
+                       const uint8_t* valid0, const uint8_t* valid1, int B, int n0, int n1, const Min& mn, uint8_t* positive,
+                       int64_t* m0, int64_t* m1, void* workspace, hipStream_t st) {
   const int nmin = imin(n0, n1), nmax = imax(n0, n1);
   char* w = static_cast<char*>(workspace);
   double* cost = reinterpret_cast<double*>(w);
@@ -517,17 +680,36 @@ hipError_t gt_line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8
   w += up256((size_t)B * n1);
   const size_t total = (size_t)B * n0 * n1;
   const unsigned rb = (unsigned)(((size_t)B * n0 + 3) / 4), cb = (unsigned)(((size_t)B * n1 + 255) / 256);
-  gl_flags<<<dim3(rb + cb), dim3(256), 0, st>>>(cnt0, cnt1t, out_of0, out_of1, valid0, valid1, B, n0, n1, ov_min, rb, dead0,
-                                                dead1, m0, m1);
+  gl_flags<Min><<<dim3(rb + cb), dim3(256), 0, st>>>(cnt0, cnt1t, out_of0, out_of1, valid0, valid1, B, n0, n1, mn, rb, dead0,
+                                                     dead1, m0, m1);
   const bool tr = n1 < n0;
   gl_cost<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(cnt0, cnt1t, dead0, dead1, total, n0, n1, tr, cost);
   // the transposed cost is stored contiguous, so the solver walks rows of unit stride either way
   hipError_t e = launch_lsa(cost, B, nmin, nmax, (size_t)nmax, 1, tr, row_ind, col_ind, w, st);
   if (e != hipSuccess) return e;
   launch_fill0(positive, total, st);
-  gl_pairs<<<dim3((unsigned)(((size_t)B * nmin + 255) / 256)), dim3(256), 0, st>>>(cnt0, cnt1t, dead0, dead1, row_ind, col_ind,
-                                                                                  B, n0, n1, nmin, ov_min, positive, m0, m1);
+  gl_pairs<Min><<<dim3((unsigned)(((size_t)B * nmin + 255) / 256)), dim3(256), 0, st>>>(cnt0, cnt1t, dead0, dead1, row_ind,
+                                                                                       col_ind, B, n0, n1, nmin, mn, positive,
+                                                                                       m0, m1);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t gt_line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
+                          const uint8_t* valid0, const uint8_t* valid1, int B, int n0, int n1, int ov_min, uint8_t* positive,
+                          int64_t* m0, int64_t* m1, void* workspace, hipStream_t st) {
+  return line_labels(cnt0, cnt1t, out_of0, out_of1, valid0, valid1, B, n0, n1, OneMin{ov_min}, positive, m0, m1, workspace, st);
+}
+
+hipError_t gt_line_labels_visibility(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
+                                     const uint8_t* ignore_depth0, const uint8_t* ignore_depth1, const uint8_t* num_visible0,
+                                     const uint8_t* num_visible1, const uint8_t* valid0, const uint8_t* valid1, int B, int n0,
+                                     int n1, int npts, const int* min_close, uint8_t* positive, int64_t* m0, int64_t* m1,
+                                     void* workspace, hipStream_t st) {
+  PerLineMin mn;
+  mn.nvis0 = num_visible0, mn.nvis1 = num_visible1, mn.ignd0 = ignore_depth0, mn.ignd1 = ignore_depth1;
+  for (int v = 0; v < 256; ++v) mn.tab.min_close[v] = (uint16_t)(v <= npts ? min_close[v] : npts + 1);
+  return line_labels(cnt0, cnt1t, out_of0, out_of1, valid0, valid1, B, n0, n1, mn, positive, m0, m1, workspace, st);
 }
 
 }  // namespace lg

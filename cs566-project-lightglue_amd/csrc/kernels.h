@@ -534,6 +534,28 @@ size_t gt_line_labels_workspace_bytes(int B, int n0, int n1);
 hipError_t gt_line_labels(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
                           const uint8_t* valid0, const uint8_t* valid1, int B, int n0, int n1, int ov_min, uint8_t* positive,
                           int64_t* m0, int64_t* m1, void* workspace, hipStream_t st);
+// Line ground truth from pose and depth (gt_lines.hip; gt_generation.py:207-406).  Stage A: a projection
+// front end (depth sampling and camera chain of gt_depth_common.h) in front of the same counting
+// kernel; besides the counts and out_of it gives, per line, the number of visible samples and whether
+// too few samples have valid depth.  out_min: gt_line_count_threshold_visibility; valid_min: the smallest
+// count of samples with valid depth that is not ignored (gt_line_count_threshold_valid_depth).  The
+// workspace is gt_line_counts_workspace_bytes.  Stage B: as gt_line_labels with a minimum count per row
+// and per column, min_close[num_visible] (gt_line_min_close_table, npts + 1 ints), out_of outside
+// mask_close and ignore_depth or-ed into the ignored lines; workspace gt_line_labels_workspace_bytes.
+struct GtLineDepthCall {
+  const float *lines0, *lines1, *depth0, *depth1, *cam0, *cam1, *T_0to1, *T_1to0;
+  int B, n0, n1, H0, W0, H1, W1, ih0, iw0, ih1, iw1, n_dist, npts, out_min, valid_min;
+  float dist_th;
+  uint8_t *cnt0, *cnt1t, *out_of0, *out_of1, *ignore_depth0, *ignore_depth1, *num_visible0, *num_visible1;
+};
+int gt_line_count_threshold_valid_depth(int npts, double min_visibility_th);
+void gt_line_min_close_table(int npts, double overlap_th, int* min_close);
+hipError_t gt_line_counts_pose_depth(const GtLineDepthCall& c, void* workspace, hipStream_t st);
+hipError_t gt_line_labels_visibility(const uint8_t* cnt0, const uint8_t* cnt1t, const uint8_t* out_of0, const uint8_t* out_of1,
+                                     const uint8_t* ignore_depth0, const uint8_t* ignore_depth1, const uint8_t* num_visible0,
+                                     const uint8_t* num_visible1, const uint8_t* valid0, const uint8_t* valid1, int B, int n0,
+                                     int n1, int npts, const int* min_close, uint8_t* positive, int64_t* m0, int64_t* m1,
+                                     void* workspace, hipStream_t st);
 // SciPy's linear_sum_assignment (rectangular_lsap) per pair, one wave each: fp64 cost [B,nr,nc] ->
 // row_ind / col_ind [B, min(nr,nc)], SciPy's own result among the optimal ones; an infeasible pair
 // (no finite assignment) gets -1 everywhere.  The workspace is only needed when the state of a pair

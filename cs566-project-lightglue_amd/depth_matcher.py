@@ -15,10 +15,10 @@ Cameras and poses are taken duck-typed: any object with a ``_data`` tensor (the 
 Differences from the reference:
 
 * ``reward`` (default True): ``False`` skips the [B, M, N] fp32 reward and omits the key.
-* ``use_lines: True`` raises at construction: the pose-and-depth line ground truth
-  (``gt_line_matches_from_pose_depth``) is out of scope.  Line ground truth from homographies is
-  ``matchers.line_homography_matcher`` (:mod:`~lightglue_amd.line_gt`), whose counting kernel and
-  assignment solver this variant would reuse behind a projection front end.
+* ``use_lines: True`` raises at construction under this name (its tests pin that).  The pose-and-depth
+  line ground truth (``gt_line_matches_from_pose_depth``) is ``matchers.line_depth_matcher``
+  (:class:`~lightglue_amd.line_gt.LineDepthMatcher`): this matcher with ``use_lines`` on by default, its
+  samples projected by the same device helpers as the keypoints here (csrc/gt_depth_common.h).
 * With no keypoints in either image the reference returns a tuple its pipeline cannot merge; here the
   dict comes back with that tuple's contents (all-false assignment, matches -1) and empty / zero rest.
 """
@@ -233,7 +233,7 @@ class DepthMatcher(BaseModel):
     def _init(self, conf):
         if conf.use_lines:
             raise NotImplementedError(
-                "depth_matcher: use_lines (line ground truth from pose and depth) is out of scope")
+                "depth_matcher: use_lines is not served under this name; use matchers.line_depth_matcher")
         if conf.use_points:  # :30-31
             self.required_data_keys += ["keypoints0", "keypoints1"]
 

@@ -8,7 +8,8 @@ model registry that resolve the matcher by name.
   ``"two_view_pipeline"`` to :class:`TwoViewPipeline`; ``"matchers.homography_matcher"`` to the
   HIP ground-truth matcher (:mod:`~lightglue_amd.gt_matcher`); ``"matchers.line_homography_matcher"`` to
   the same with line ground truth (:mod:`~lightglue_amd.line_gt`); ``"matchers.depth_matcher"`` to the
-  pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`); ``"matchers.nearest_neighbor_matcher"`` to
+  pose-and-depth one (:mod:`~lightglue_amd.depth_matcher`) and ``"matchers.line_depth_matcher"`` to that
+  with line ground truth (:mod:`~lightglue_amd.line_gt`); ``"matchers.nearest_neighbor_matcher"`` to
   the nearest-neighbour baseline (:mod:`~lightglue_amd.nn_matcher`); ``"extractors.superpoint_open"`` to
   the open SuperPoint (:mod:`~lightglue_amd.superpoint_open`); ``"extractors.aliked"`` to ALIKED
   (:mod:`~lightglue_amd.aliked`); ``"matchers.gluestick"`` to the point-and-line matcher
@@ -199,6 +200,12 @@ def _depth_matcher():
     return DepthMatcher
 
 
+def _line_depth_matcher():
+    from .line_gt import LineDepthMatcher
+
+    return LineDepthMatcher
+
+
 def _nn_matcher():
     from .nn_matcher import NearestNeighborMatcher
 
@@ -230,7 +237,7 @@ def _lsd():
 
 
 _LAZY = (_superpoint, _superpoint_open, _aliked, _superglue, _gluestick, _homography_matcher, _line_homography_matcher,
-         _depth_matcher, _nn_matcher, _wireframe, _lsd)
+         _depth_matcher, _line_depth_matcher, _nn_matcher, _wireframe, _lsd)
 
 _REGISTRY = {
     "lightglue": LightGlue,
@@ -270,6 +277,9 @@ _REGISTRY = {
     # the pose-and-depth ground truth (matchers/depth_matcher.py), resolved lazily
     "matchers.depth_matcher": _depth_matcher,
     "depth_matcher": _depth_matcher,
+    # the same with line ground truth (use_lines, which the two names above refuse), resolved lazily
+    "matchers.line_depth_matcher": _line_depth_matcher,
+    "line_depth_matcher": _line_depth_matcher,
     # the nearest-neighbour baseline (matchers/nearest_neighbor_matcher.py), resolved lazily
     "matchers.nearest_neighbor_matcher": _nn_matcher,
     "nearest_neighbor_matcher": _nn_matcher,

@@ -355,6 +355,57 @@ int lg_gt_line_labels(const uint8_t* num_close_pts0, const uint8_t* num_close_pt
                       int32_t n1, int32_t npts, double overlap_th, uint8_t* positive_u8, int64_t* line_matches0,
                       int64_t* line_matches1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Line ground truth from pose and depth: gt_line_matches_from_pose_depth
+ * (gluefactory/geometry/gt_generation.py:207-406 with sample_pts, sample_depth, project and
+ * torch_perp_dist), what matchers.depth_matcher computes with use_lines.  Five more entries under
+ * ABI 12.  No handle.  Two stages as above; running lg_gt_line_labels_visibility on the outputs of
+ * lg_gt_line_counts_pose_depth gives the reference's (positive, m0, m1).
+ *
+ * Stage A, lg_gt_line_counts_pose_depth.  Device inputs, fp32: lines0 [B,n0,4], lines1 [B,n1,4];
+ * depth0 [B,H0,W0], depth1 [B,H1,W1]; cam0, cam1 [B, 6 + n_dist] and T_0to1, T_1to0 [B,12] as in
+ * lg_gt_matches_from_pose_depth.  image_h0 .. image_w1: the image sizes the out-of-image test uses; the
+ * endpoints are clamped to the depth maps' sizes.  Per sample: the depth (bilinear over the map with
+ * values <= 0 as NaN, the nearest sample where that is NaN, zero padding), image2cam, times the depth,
+ * T.transform, cam2image, without a consistency check; visible = valid depth & cam2image's valid.  A
+ * sample without depth projects to NaN and is neither outside nor close to anything; a sample that is
+ * not visible counts for nothing.  Device outputs, all uint8: num_close_pts0, num_close_pts1_t
+ * [B,n0,n1] and out_of0 [B,n1], out_of1 [B,n0] as above; ignore_depth0 [B,n0], ignore_depth1 [B,n1]
+ * (mean(valid depth) < min_visibility_th); num_visible0 [B,n0], num_visible1 [B,n1] (visible samples
+ * of the line).  The workspace holds the projected samples (8 npts + 32 bytes per line).
+ *
+ * Stage B, lg_gt_line_labels_visibility.  Device inputs, uint8: the eight outputs of stage A and
+ * valid_lines0 / valid_lines1.  mask_close compares num_close_pts1_t[i,j] with num_visible0[i] *
+ * overlap_th and num_close_pts0[i,j] with num_visible1[j] * overlap_th (fp32, as the reference);
+ * out_of only makes a line unmatched; a line is ignored when it is invalid or its ignore_depth is set.
+ * Outputs and workspace as lg_gt_line_labels.
+ *
+ * lg_gt_line_depth_thresholds: the integer thresholds the kernels compare counts with: min_close
+ * [npts + 1], min_close[v] the smallest count c with float(c) > float(v) * overlap_th (npts + 1: none);
+ * the smallest count of outside samples that makes a line "out"; the smallest count of samples with
+ * valid depth that is not ignored.
+ *
+ * Stream-ordered, asynchronous, no atomics, identical results run to run.  LG_E_INVALID as for the
+ * entries above, and n_dist outside {0, 2, 4} or an empty depth map.  B, n0 or n1 == 0: LG_OK, nothing
+ * launched, no output written. */
+int lg_gt_line_depth_thresholds(int32_t npts, double min_visibility_th, double overlap_th, int32_t* min_close,
+                                int32_t* out_min_count, int32_t* valid_min_count);
+int lg_gt_line_counts_pose_depth_workspace_bytes(int32_t B, int32_t n0, int32_t n1, int32_t npts, size_t* bytes);
+int lg_gt_line_counts_pose_depth(const float* lines0, const float* lines1, const float* depth0, int32_t H0, int32_t W0,
+                                 const float* depth1, int32_t H1, int32_t W1, int32_t image_h0, int32_t image_w0,
+                                 int32_t image_h1, int32_t image_w1, const float* cam0, const float* cam1, int32_t n_dist,
+                                 const float* T_0to1, const float* T_1to0, int32_t B, int32_t n0, int32_t n1, int32_t npts,
+                                 double dist_th, double min_visibility_th, uint8_t* num_close_pts0, uint8_t* num_close_pts1_t,
+                                 uint8_t* out_of0, uint8_t* out_of1, uint8_t* ignore_depth0, uint8_t* ignore_depth1,
+                                 uint8_t* num_visible0, uint8_t* num_visible1, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int lg_gt_line_labels_visibility_workspace_bytes(int32_t B, int32_t n0, int32_t n1, size_t* bytes);
+int lg_gt_line_labels_visibility(const uint8_t* num_close_pts0, const uint8_t* num_close_pts1_t, const uint8_t* out_of0,
+                                 const uint8_t* out_of1, const uint8_t* ignore_depth0, const uint8_t* ignore_depth1,
+                                 const uint8_t* num_visible0, const uint8_t* num_visible1, const uint8_t* valid_lines0,
+                                 const uint8_t* valid_lines1, int32_t B, int32_t n0, int32_t n1, int32_t npts,
+                                 double overlap_th, uint8_t* positive_u8, int64_t* line_matches0, int64_t* line_matches1,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* Batched linear sum assignment: SciPy's scipy.optimize.linear_sum_assignment (rectangular_lsap, the
  * shortest-augmenting-path solver) for every pair of a batch, one wave per pair.  Device input: cost
  * [B,nr,nc] fp64, finite.  Device outputs: row_ind, col_ind [B, min(nr,nc)] int64, row_ind ascending.
